@@ -24,6 +24,8 @@ region; N > 1: the scalar mask all-reduce and the gradient exchange are issued e
 cannot be recorded inside a captured graph, so `roofline` / `kernels` come from the same K steps issued eagerly right
 after (`eager` reports their wall time).  `--exec eager` times ordinary stream launches.  If the capture fails on any
 rank, or replaying is not faster than eager launches in a short untimed trial, the run falls back to eager.
+`--dump-outputs DIR` writes what the last timed step computed (loss and every parameter gradient) as DIR/<name>.npy: the
+inputs are seeded, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -74,7 +76,16 @@ def parse():
     ap.add_argument("--train-steps", type=int, default=10,
                     help="after the fwd+bwd measurement: time this many full training iterations (fwd+bwd + the two Adam "
                          "solvers with weight decay, python/train.py:136-148) and report them as `train_step`; 0 = skip")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed -- the loss and every parameter "
+                         "gradient -- as DIR/<name>.npy (float32, at most 64 MB in all; a grid gradient that does not fit "
+                         "is written as a fixed, seeded, uniform sample of its rows, DIR/<name>.sample.npy, with the row "
+                         "indices in DIR/<name>.sample_rows.npy (float64); only the cells the step's points touch hold "
+                         "gradient, so most sampled rows are zero).  N > 1: rank 0's arrays.  dumps/ is ignored by git")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 from ndjir_amd.step import Step  # noqa: E402,F401  (the step itself lives in the package; bench.py only times it)
@@ -232,6 +243,45 @@ def fp32_engine_leg(step, steps=10):
     finally:
         del graph
         mlp.set_math(old)
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE_SEED = 412
+
+
+def dump_outputs(step, loss, out_dir):
+    """`--dump-outputs`: what the timed path hands its caller after the last timed step -- the loss, the MLP gradients (the
+    views of the flat bucket) and the grid gradients (the accumulate-in-place buffers) -- as out_dir/<name>.npy, float32,
+    DUMP_LIMIT_BYTES in all at most.  A grid gradient too large for what is left is written as a uniform sample of its rows
+    (<name>.sample) with their row indices (<name>.sample_rows, float64: exact); the indices depend on the buffer's shape and
+    a fixed seed only, so two builds run with the same arguments dump the same rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(-1)}
+    for name, v in zip(step.mlp_names, step.grad_views):
+        arrays["grad." + name.replace("/", ".")] = v
+    used = sum(t.numel() * 4 for t in arrays.values())
+    slack = 4096 * (len(arrays) + 2 * len(step.grid_bufs))      # .npy headers (a sample comes with its row indices)
+    grids = list(step.grid_bufs.items())
+    for i, (name, buf) in enumerate(grids):
+        share = (DUMP_LIMIT_BYTES - slack - used) // (len(grids) - i)
+        rows = buf.view(-1, buf.shape[-1])
+        key = "grad." + name.replace("/", ".")
+        if rows.numel() * 4 > share:
+            k = share // (4 * rows.shape[1] + 8)                 # a row of floats + its float64 index
+            idx = np.unique(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, rows.shape[0], size=k))
+            arrays[key + ".sample_rows"] = torch.from_numpy(idx.astype(np.float64))
+            key, buf = key + ".sample", rows.index_select(0, torch.from_numpy(idx).to(rows.device))
+            used += idx.size * 8
+        arrays[key] = buf
+        used += buf.numel() * 4
+    total = 0
+    for name, t in arrays.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, t.detach().cpu().numpy() if t.dtype == torch.float64 else t.detach().float().cpu().numpy())
+        total += os.path.getsize(path)
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs wrote {total} bytes (limit {DUMP_LIMIT_BYTES})"
+    print(f"dump-outputs: {len(arrays)} arrays, {total / 1e6:.1f} MB -> {out_dir}", file=sys.stderr, flush=True)
 
 
 def _all_ranks_ok(step, ok):
@@ -590,6 +640,14 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if os.environ.get("NDJIR_BENCH_SAME_DEVICE"):
         local_rank = 0      # debugging aid: several ranks on ONE GPU over gloo, to exercise the N > 1 code path
+    elif world > 1:
+        # one RCCL rank per device of this node: with fewer devices than local ranks, every rank of the node stops here,
+        # before the process group (a rank would otherwise die on a device ordinal that does not exist while its peers
+        # wait for it in the rendezvous)
+        local_world, n_dev = int(os.environ.get("LOCAL_WORLD_SIZE", str(world))), torch.cuda.device_count()
+        if n_dev < local_world:
+            sys.exit(f"bench.py rank {rank}: {local_world} ranks on this node, one per GPU over RCCL, but {n_dev} GPU(s) visible "
+                     "(NDJIR_BENCH_SAME_DEVICE=1 runs the ranks on GPU 0 over gloo)")
     force_dist = world == 1 and bool(os.environ.get("NDJIR_BENCH_FORCE_DIST"))
     if world > 1 or force_dist:
         import torch.distributed as dist
@@ -681,6 +739,8 @@ def main():
             barrier()
             el = time.perf_counter() - t0
             exec_mode = "eager (graph replay rejected)"
+        if a.dump_outputs and rank == 0:
+            dump_outputs(step, loss, a.dump_outputs)
         # HIP events cannot be recorded inside a captured graph: the same K steps are issued once more as
         # ordinary stream launches, with events around every engine launch, for `roofline` / `kernels`
         mlp.PROFILE = [] if rank == 0 else None
@@ -706,6 +766,8 @@ def main():
             loss = step.forward_backward()
         barrier()
         el = time.perf_counter() - t0
+        if a.dump_outputs and rank == 0:
+            dump_outputs(step, loss, a.dump_outputs)
     else:
         barrier()
         mlp.PROFILE = []
@@ -715,6 +777,8 @@ def main():
         barrier()
         el = time.perf_counter() - t0
         profile, mlp.PROFILE = mlp.PROFILE, None
+        if a.dump_outputs:
+            dump_outputs(step, loss, a.dump_outputs)
     ranks_info = None
     if world > 1:
         # what the collective library saw: one line per rank (device, its own time over the timed region), so that a scaling

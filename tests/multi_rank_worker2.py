@@ -1,6 +1,6 @@
 """Worker of tests/test_gpu_multirank.py (all ranks share GPU 0 over gloo -- the only multi-rank set-up a single-GPU box offers).
 usage (under torch.distributed.run): python tests/multi_rank_worker2.py <mode> <outdir>
-  exchange   the HIP sparse grid-gradient exchange at the launcher's world size (4, 8: 3 / 7 remote lists): result against a
+  exchange   the HIP sparse grid-gradient exchange at the launcher's world size (3, 4: 2 / 3 remote lists): result against a
              dense all-reduce; then a FORCED overflow (the wire size cut below the lists) -> device flag, statistics, an
              incomplete sum; then the wire size grows at the next look (every CHECK_EVERY exchanges) and the sum is whole again
   grow       the query points GROW between exchanges beyond the list capacity the first exchange sized: rows

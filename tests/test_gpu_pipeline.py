@@ -375,6 +375,46 @@ def test_bench_step_graph_replay_matches_eager(gpu):
             assert float((a - b).abs().max()) <= 1e-5 * max(float(b.abs().max()), 1e-12)
 
 
+@pytest.mark.timeout(900)
+def test_bench_dump_outputs_are_the_timed_steps_results(gpu, tmp_path):
+    """`bench.py --dump-outputs DIR` (a child process, as a user runs it): the loss of the JSON line and every parameter
+    gradient of the last timed step, as float32 .npy files -- equal to the same step run here.  (The bench replays one set of
+    inputs, so every timed step computes the same arrays: this checks that the dump is the timed path's result -- names,
+    dtype, no stale or zero buffer --, not which of the timed steps wrote it.)"""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    from ndjir_amd import config as cfg
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--rays", "64", "--override", "geometric_network.voxel.grid_size=64",
+           "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra-legs", "--train-steps", "0",
+           "--dump-outputs", str(tmp_path)]
+    res = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=800)
+    assert res.returncode == 0, res.stderr[-3000:]
+    d = json.loads(res.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    got = {f[:-len(".npy")]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert float(got["loss"][0]) == pytest.approx(d["loss"], rel=1e-7)
+    step = bench.Step(cfg.load("default", ["geometric_network.voxel.grid_size=64"]), 64, gpu, 0, 1)
+    try:
+        for _ in range(2):
+            loss = step.forward_backward()
+        torch.cuda.synchronize()
+        want = {"grad." + k.replace("/", "."): v for k, v in zip(step.mlp_names, step.grad_views)}
+        want.update({"grad." + k.replace("/", "."): v for k, v in step.grid_bufs.items()})     # 64^3 x 4: whole, no sample
+        assert set(got) == set(want) | {"loss"}
+        assert float(got["loss"][0]) == pytest.approx(float(loss), rel=1e-6)
+        for k, v in want.items():
+            ref = v.cpu().numpy()
+            assert got[k].shape == ref.shape, k
+            assert float(np.abs(got[k] - ref).max()) <= 1e-5 * max(float(np.abs(ref).max()), 1e-12), k
+    finally:
+        step.close()
+
+
 @pytest.mark.parametrize("case", ["all_miss", "single_ray", "ragged_rays"])
 def test_step_edge_cases(gpu, case):
     """Whole step (sampler included) on degenerate ray batches vs the oracle: every ray missing the box (all masks zero:
