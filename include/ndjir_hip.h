@@ -642,7 +642,7 @@ int ndjir_mlp_wgrad_group(int n_src, const float* const* A, const int* lda, cons
                           const int* ex_n, const int* ex_S, const int* ex_stride, const int* ex_accum, const int* layout,
                           hipStream_t stream);
 /* layout (host array of n_src ints, or NULL = every operand row-major): bit 0 = A[i] is point-blocked (ndjir_mlp_chain accum_y
- * bit 3; lda[i] = its ld_side), bit 1 = B[i] is; a blocked operand needs P[i] % 32 == 0.  The same array goes to
+ * bit 3; lda[i] = its ld_side), bit 1 = B[i] is; a blocked operand needs P[i] % 32 == 0 (NDJIR_ERR_ARG otherwise, before any launch).  The same array goes to
  * ndjir_mlp_wgrad_group_workspace (it decides which outputs <= 8 wide take the streaming path). */
 /* Bias gradient of a layer: out (N) (+)= column sums of its deltas X (P x N, row stride ldx); the
  * reference gets it from nnabla's affine backward (a reduction kernel per layer). */

@@ -34,7 +34,13 @@ __device__ __forceinline__ AlphaTerms alpha_terms(float sdf, float nx, float ny,
   o.s0 = sdf - o.ic * o.delta * 0.5f;
   o.c0 = rd_sigmoid(gain * o.s0);
   o.c1 = rd_sigmoid(gain * o.s1);
-  o.q = (o.c0 - o.c1 + 1e-5f) / (o.c0 + 1e-5f);
+  // c0 - c1 without the cancellation: sigmoid(x0) - sigmoid(x1) = sigmoid(x0) sigmoid(-x1) (1 - exp(-(x0 - x1))) with
+  // x0 - x1 = -gain ic delta.  Far outside the surface both sigmoids round to within an ulp of 1 and their difference, a few
+  // 1e-5 beside the 1e-5 of the numerator, keeps 3 digits: on a ray that grazes the object every alpha is that small, and the
+  // pixel normal and roughness -- ratios of such sums -- came out 1e-5 off, which the specular term's d/d roughness at
+  // roughness -> 0 multiplies by ~1e3 (DESIGN.md changelog).
+  const float dc = o.c0 * rd_sigmoid(-gain * o.s1) * -expm1f(gain * (o.ic * o.delta));
+  o.q = (dc + 1e-5f) / (o.c0 + 1e-5f);
   o.a = fminf(fmaxf(o.q, 0.f), 1.f);
   return o;
 }

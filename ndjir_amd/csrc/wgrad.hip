@@ -2009,6 +2009,8 @@ int launch_wgrad_group(int n_src, const float* const* A, const int* lda, const f
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_group_wide), hipFuncAttributeMaxDynamicSharedMemorySize, WGP_LDS_WIDE);
     attr = true;
   }
+  // (the one caller, ndjir_mlp_wgrad_group, has refused layout bits on an operand that is not whole 32-point blocks: k_wgg_absmax and
+  //  the blocked loaders read every block to its end -- tests/test_gpu_wgrad.py pins that)
   if (n_src > 65536) return NDJIR_ERR_ARG;
   for (int i = 0; i < n_src; ++i)
     if (out_id[i] < 0 || out_id[i] >= n_out) return NDJIR_ERR_ARG;
@@ -2064,7 +2066,11 @@ int launch_wgrad_group(int n_src, const float* const* A, const int* lda, const f
     static int order[6] = {5, 4, 1, 2, 0, 3};
     static const bool order_env = [] {
       const char* e = getenv("NDJIR_WGG_ORDER");          // A/B switch, e.g. 530412 = the order of rounds 4 - 5
-      if (e && strlen(e) == 6) for (int i = 0; i < 6; ++i) order[i] = e[i] - '0';
+      if (e && strlen(e) == 6) {          // a permutation of 0..5, or ignored: a kind left out would never be issued
+        int seen = 0;
+        for (int i = 0; i < 6; ++i) seen |= (e[i] >= '0' && e[i] <= '5') ? 1 << (e[i] - '0') : 0;
+        if (seen == 63) for (int i = 0; i < 6; ++i) order[i] = e[i] - '0';
+      }
       return true;
     }();
     (void)order_env;

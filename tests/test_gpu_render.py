@@ -72,6 +72,35 @@ def test_alpha_weights_matches_composite(gpu, B, R, N, Nb, opaque):
         assert err < max(4.0 * err_stock, 1e-5), (name, err, err_stock)
 
 
+def test_alpha_far_outside_the_surface_keeps_its_relative_accuracy(gpu):
+    """Rays that pass the object at a distance: gain * sdf in [8, 16], so both sigmoids are within 3e-4 of 1 and alpha =
+    (c0 - c1 + 1e-5) / (c0 + 1e-5) is 1e-5 ... 3e-4.  Their fp32 difference carries 2^-24 absolute, 1e-4 ... 3e-3 of such an
+    alpha; the pixel normal and the pixel roughness of a grazing ray are ratios of sums of these, and the specular term's
+    d / d roughness at roughness -> 0 multiplied that error into a 6e-3 distance of the roughness net's gradients from fp64
+    (test_step_parity_given_samples[custom-32-*]).  The kernel forms c0 - c1 as sigmoid(x0) sigmoid(-x1) (1 - exp(x1 - x0)).
+    Bound 2^-18 relative, per sample: x1 = gain * s1 (|x1| <= 16) carries two fp32 roundings, 2 * 2^-24 * 16 = 1.9e-6
+    absolute, which is the relative error of sigmoid(-x1) ~ exp(-x1); expf / expm1f (2 ulp each), the argument of expm1f
+    (3 roundings) and the remaining 5 operations add 15 * 2^-24 = 0.9e-6.  Measured: 8.2e-7 (the fp32 composite with the subtraction: 1.2e-2)."""
+    from ndjir_amd.volume import alpha_weights
+    B, R, N, Nb = 1, 40, 128, 1
+    rng = np.random.RandomState(5)
+    r32 = lambda a: torch.tensor(np.asarray(a, np.float32), device=gpu)
+    sdf = r32(0.2 + 0.2 * rng.rand(B, R, N, 1))
+    n, rd = rng.randn(B, R, N, 3), rng.randn(B, R, 3)
+    n, rd = r32(n / np.linalg.norm(n, axis=-1, keepdims=True)), r32(rd / np.linalg.norm(rd, axis=-1, keepdims=True))
+    t = r32((np.arange(N + 1).reshape(1, 1, N + 1, 1) + 0.5 * rng.rand(B, R, N + 1, 1)) * (3.0 / N))
+    gain, car = r32([40.0]), r32([0.3])
+    mask, abg = torch.ones(B, R, 1, 1, device=gpu), r32(rng.rand(B, R, Nb, 1) * 0.2)
+    ins = (sdf, n, rd, t, gain, car, mask, abg)
+    ref = composite_alpha_weights(*[v.double() for v in ins])[0]
+    assert 1e-5 <= float(ref.min()) and float(ref.max()) < 1e-3
+    out = alpha_weights(*ins)[0]
+    rel = float(((out.double() - ref).abs() / ref).max())
+    stock = float(((composite_alpha_weights(*ins)[0].double() - ref).abs() / ref).max())
+    print(f"alpha far outside: max relative error {rel:.2e} (fp32 composite with the subtraction: {stock:.2e}), bound {2.0 ** -18:.2e}")
+    assert rel <= 2.0 ** -18, (rel, stock)
+
+
 @pytest.mark.parametrize("R,S_all,off,S,C", [(50, 160, 0, 128, 256), (50, 160, 128, 32, 3), (7, 128, 0, 128, 1),
                                              (3, 33, 0, 33, 6), (9, 160, 0, 128, 300)])
 def test_integrate_matches_composite(gpu, R, S_all, off, S, C):
