@@ -715,6 +715,38 @@ int ndjir_solver_veto_if_nan(int n, const float* x, int* flag_a, int* flag_b, hi
 /* *out += sum x^2 (device double): the norm of `clip_grad_by_norm` (python/solver.py:53-58) */
 int ndjir_solver_sum_squares(long long n, const float* x, double* out, hipStream_t stream);
 
+/* ---- mesh export: vertex textures and the environment map -------------------------------------------
+ * Replaces the per-texture evaluation of `save_attributed_mesh` (python/extract_by_mc.py:197-223: geometric net + nn.grad
+ * + one material net, six times per vertex) by one head over the raw (pre-activation) outputs of the four material nets
+ * for N vertices: implicit illumination (N,ci), base colour (N,3), roughness (N,2) = [value, std], specular reflectance
+ * (N,2 cs) = [value x cs, std x cs], ci and cs in {1, 3}.  textures = host array of six device pointers, each (N,3):
+ * base_color = sigmoid (python/network.py:262); implicit_illumination = act_last (:331-334; implicit_act 1 softplus with
+ * implicit_beta, 2 sigmoid, 3 relu), blue if ci == 1; roughness = clamp(sigmoid [^2 if remap], lower bound, 1)
+ * (:456-463), green; specular_reflectance = 0.16 s^2 if remap else specular_scale * s (:498-508), red if cs == 1;
+ * roughness_std, specular_reflectance_std = softplus of the std outputs, placed likewise.  Every value is clipped to
+ * [0, 1] and channels nothing is placed in are 0 (`create_rgb_color`, extract_by_mc.py:187-194).  std_max (2 ints, zeroed
+ * by the caller before the first call): running maxima of the two clipped std textures as fp32 bit patterns, combined
+ * over calls (chunks) by integer atomic max -- order-independent. */
+int ndjir_bake_head(long long N, const float* raw_implicit, const float* raw_base_color, const float* raw_roughness,
+                    const float* raw_specular, int implicit_channels, int specular_channels, int implicit_act,
+                    float implicit_beta, int remap, float roughness_lower_bound, float specular_scale,
+                    float* const* textures, int* std_max, hipStream_t stream);
+/* `vertex_colors / vertex_colors.max()` (python/extract_by_mc.py:215-216) of the two std textures (N,3) in place, the
+ * maxima taken from std_max after the last ndjir_bake_head call of the mesh. */
+int ndjir_bake_scale(long long N, float* roughness_std, float* specular_std, const int* std_max, hipStream_t stream);
+/* The H x 2H lattice of light directions of `extract_environment_map` (python/extract_by_mc.py:227-237) as dirs
+ * (H * 2H, 3): row angle a_i = linspace(0, pi, H)[i], column angle b_j = linspace(-pi, pi, 2H)[j] (the reference's
+ * variable names are swapped, :231), (x, y, z) = (cos a sin b, sin a sin b, cos b); arithmetic in double like numpy's,
+ * rounded once to fp32.  H >= 2. */
+int ndjir_envmap_directions(int H, float* dirs, hipStream_t stream);
+/* python/extract_by_mc.py:242-255: intensity (H * W, C), C in {1, 3}, with its minimum and maximum min_max (2 floats on
+ * the device) -> uint8 image: x * 255 if sigmoid_mode, else x / max * 255 if min != max, else 255; clipped to
+ * [0, 255] and truncated.  image is what a reader decodes from the file the reference writes: (H, W, 3) in the
+ * network's channel order (the `[..., ::-1]` of :255 and the writer's BGR convention cancel) or, for C == 1, (H, W)
+ * mirrored left-right (there :255 reverses the columns, sic). */
+int ndjir_envmap_quantize(int H, int W, int C, const float* intensity, const float* min_max, int sigmoid_mode,
+                          unsigned char* image, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

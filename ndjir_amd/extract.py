@@ -10,11 +10,29 @@ in the reference, `extract_by_mc.py:31-43`).
 
 The lattice shards over x-slabs: `slab_range(G, rank, world)`; each rank evaluates its slabs independently
 (no collective on the data path), `gather_volume` concatenates them.
+
+Export half (`compute_vertex_colors`, `create_rgb_color`, `save_attributed_mesh`, `extract_environment_map`, `extract`;
+extract_by_mc.py:144-261): the caller brings the mesh (vertices and faces, e.g. from marching cubes over `compute_vol`).
+`bake_vertex_attributes` evaluates the geometric net with its gradient once per vertex and the four material nets once on
+the packed input, and one head launch (csrc/bake.hip) turns their raw outputs into the six textures -- the reference runs
+the geometric net and `nn.grad` six times per vertex, once per texture.  `extract_environment_map` builds the direction
+lattice, evaluates the environment light net and quantises on the device.  Out of scope: marching cubes, mask trimming
+and mesh splitting (`clean_points_by_mask`, `create_trimmed_meshes`, `create_largest_meshes`, :77-141: cv2 morphology and
+connected components), and sharding the vertices over ranks.
 """
+import os
+
 import numpy as np
 import torch
 
+from . import lib
+from . import meshio
 from .network import geometric_network
+
+# the six textures in the reference's order (extract_by_mc.py:198-208)
+TEXTURES = ("base_color", "implicit_illumination", "roughness", "specular_reflectance", "roughness_std",
+            "specular_reflectance_std")
+_LAST_ACTS = {"softplus": 1, "sigmoid": 2, "relu": 3}
 
 
 def lattice_axes(mins, maxs, grid_size):
@@ -72,3 +90,145 @@ def compute_pts_vol(mins, maxs, grid_size, conf, **kw):
     pts = np.stack((X.reshape(-1), Y.reshape(-1), Z.reshape(-1)), axis=1)
     vol = compute_vol(mins, maxs, grid_size, conf, **kw)
     return pts, vol.cpu().numpy()
+
+
+def _place(v, dim):
+    """`create_rgb_color` (extract_by_mc.py:187-194): clip to [0, 1]; a one-channel output goes to channel `dim` of zeros."""
+    v = v.clamp(0.0, 1.0)
+    if v.shape[-1] == 3:
+        return v
+    out = torch.zeros((v.shape[0], 3), device=v.device, dtype=v.dtype)
+    out[:, dim:dim + 1] = v
+    return out
+
+
+def bake_vertex_attributes(points, conf, chunk=1 << 18, device=None):
+    """The six vertex textures of `save_attributed_mesh` (extract_by_mc.py:197-216) for `points` (N, 3), numpy or torch,
+    cast to fp32.  Returns a dict of GPU tensors: the textures of `TEXTURES`, each (N, 3) float32 in [0, 1] with the net's
+    output placed as the reference places it (one-channel implicit illumination -> blue, roughness -> green, one-channel
+    specular reflectance -> red, other channels 0) and the two `_std` textures divided by their maximum over ALL vertices
+    (:215-216), plus `normal` (N, 3), the raw SDF gradient the nets are fed (:156, not normalised), and `sdf` (N, 1).
+
+    Points go through in chunks of `chunk`.  Where `material_nets_raw` evaluates the four nets as one operator, their raw
+    outputs go to `ndjir_bake_head`; otherwise (relu nets, weight normalisation, ...) the per-net functions and stock ops do
+    the same.  `specular_reflectance_network.fixme=true` raises: the reference's net then returns one constant and no std
+    (python/network.py:475-476), which its own `vc[out_index]` (:158-159) indexes into.  Vertices are not sharded over ranks."""
+    from . import parameter as P
+    from .network import (base_color_network, geometric_network_with_grad, implicit_illumination_network, material_nets_raw,
+                          roughness_network, specular_reflectance_network, uses_fused_geometric)
+    if conf.specular_reflectance_network.fixme:
+        raise ValueError("specular_reflectance_network.fixme=true: the net has no std output to bake "
+                         "(python/network.py:475-476 returns a constant, extract_by_mc.py:158-159 indexes it)")
+    device = device or P.get_device()
+    if not torch.is_tensor(points):
+        points = torch.from_numpy(np.ascontiguousarray(np.asarray(points, dtype=np.float32)))
+    pts = points.detach().to(device=device, dtype=torch.float32).reshape(-1, 3).contiguous()
+    N = pts.shape[0]
+    out = {name: torch.empty((N, 3), device=device, dtype=torch.float32) for name in TEXTURES}
+    out["normal"] = torch.empty((N, 3), device=device, dtype=torch.float32)
+    out["sdf"] = torch.empty((N, 1), device=device, dtype=torch.float32)
+    if N == 0:
+        return out
+    ci, cs = conf.implicit_illumination_network, conf.specular_reflectance_network
+    remap = int(conf.specular_brdf.model == "filament" and bool(conf.specular_brdf.remap))
+    fused_geo = uses_fused_geometric(conf)
+    std_max = torch.zeros(2, device=device, dtype=torch.int32)
+    head = None
+    for p0 in range(0, N, int(chunk)):
+        p1 = min(N, p0 + int(chunk))
+        x = pts[p0:p1]
+        # the fused geometric pass produces d(sdf)/dx itself; otherwise the normal comes from autograd (as in render_image)
+        with (torch.no_grad() if fused_geo else torch.enable_grad()):
+            if not fused_geo:
+                x = x.clone().requires_grad_(True)
+            sdf, feat, _, normal, Z = geometric_network_with_grad(x, conf, packed=True)
+        with torch.no_grad():
+            x, sdf, feat, normal = x.detach(), sdf.detach(), feat.detach(), normal.detach()
+            out["sdf"][p0:p1] = sdf
+            out["normal"][p0:p1] = normal
+            raws = material_nets_raw(x, feat, normal, conf, packed=Z.detach() if Z is not None else None)
+            if head is None:
+                head = raws is not None
+            if head:
+                raw_imp, raw_bc, raw_r, raw_s = (t.contiguous() for t in raws)
+                lib.call("bake_head", p1 - p0, raw_imp, raw_bc, raw_r, raw_s, raw_imp.shape[-1], raw_s.shape[-1] // 2,
+                         _LAST_ACTS[ci.act_last], float(ci.inverse_black_degree), remap, float(conf.roughness_network.lower_bound),
+                         float(cs.upper_bound_scale), [out[name][p0:p1] for name in TEXTURES], std_max)
+            else:
+                r, r_std = roughness_network(x, feat, normal, conf)
+                s, s_std = specular_reflectance_network(x, feat, normal, conf)
+                for name, v, dim in (("base_color", base_color_network(x, feat, normal, conf), 0),
+                                     ("implicit_illumination", implicit_illumination_network(x, feat, normal, conf), 2),
+                                     ("roughness", r, 1), ("specular_reflectance", s, 0), ("roughness_std", r_std, 1),
+                                     ("specular_reflectance_std", s_std, 0)):
+                    out[name][p0:p1] = _place(v, dim)
+    if head:
+        lib.call("bake_scale", N, out["roughness_std"], out["specular_reflectance_std"], std_max)
+    else:
+        for name in ("roughness_std", "specular_reflectance_std"):
+            out[name].div_(out[name].max())
+    return out
+
+
+def environment_map_directions(H, device=None):
+    """The (H * 2H, 3) lattice of light directions of extract_by_mc.py:227-237 (ndjir_envmap_directions)."""
+    from . import parameter as P
+    device = device or P.get_device()
+    dirs = torch.empty((H * 2 * H, 3), device=device, dtype=torch.float32)
+    lib.call("envmap_directions", H, dirs)
+    return dirs
+
+
+def quantize_environment_map(intensity, H, W, sigmoid_mode):
+    """extract_by_mc.py:242-255 on the device: intensity (H * W, C) float32 -> uint8 (H, W, 3) or (H, W), the pixels a reader
+    decodes from the reference's file (ndjir_envmap_quantize).  Returns (image, min_max), min_max a (2,) device tensor."""
+    C = intensity.shape[-1]
+    x = intensity.detach().reshape(H * W, C).contiguous()
+    m, M = torch.aminmax(x)
+    min_max = torch.stack([m, M])
+    image = torch.empty((H, W, 3) if C == 3 else (H, W), device=x.device, dtype=torch.uint8)
+    lib.call("envmap_quantize", H, W, C, x, min_max, int(bool(sigmoid_mode)), image)
+    return image, min_max
+
+
+def extract_environment_map(dirname, conf, H=256):
+    """`extract_environment_map` (extract_by_mc.py:226-261): writes `environment_map.png` and
+    `environment_map_min_max.txt` into `dirname`; returns dict(image uint8 ndarray, min, max, intensity (H * 2H, C) GPU
+    tensor).  For three channels the file's RGB is the net's RGB; for one channel the image is mirrored left-right, as
+    the reference's is (:255, sic)."""
+    from .network import environment_light_network
+    W = 2 * H
+    with torch.no_grad():
+        dirs = environment_map_directions(H)
+        intensity = environment_light_network(dirs.view(1, 1, H * W, 3), conf).reshape(H * W, -1)
+        if not bool(torch.isfinite(intensity).all()):
+            raise ValueError("environment light network returned non-finite intensities")
+        image, min_max = quantize_environment_map(intensity, H, W, conf.environment_light_network.act_last == "sigmoid")
+    m, M = (np.float32(v) for v in min_max.cpu().numpy())
+    image = image.cpu().numpy()
+    meshio.write_png(os.path.join(dirname, "environment_map.png"), image)
+    meshio.write_min_max(os.path.join(dirname, "environment_map_min_max.txt"), m, M)
+    return dict(image=image, min=m, max=M, intensity=intensity)
+
+
+def save_attributed_mesh(dirname, fname, verts, faces, conf, train=False, type="raw", idx=0):
+    """`save_attributed_mesh` (extract_by_mc.py:197-223) for a mesh the caller brings: bakes once and writes the six files
+    `{fname}_{G}grid_{type}_{texture}_mesh{idx:02d}.obj` (vertex colours = the texture, vertex normals = the normalised SDF
+    gradient); returns the last path, like the reference."""
+    G = conf.extraction.rough_grid_size if train else conf.extraction.grid_size
+    verts = np.ascontiguousarray(np.asarray(verts.detach().cpu() if torch.is_tensor(verts) else verts, dtype=np.float32)).reshape(-1, 3)
+    faces = np.asarray(faces.detach().cpu() if torch.is_tensor(faces) else faces).reshape(-1, 3)
+    baked = bake_vertex_attributes(verts, conf)
+    normals = meshio.normalize_rows(baked["normal"].cpu().numpy())
+    fpath = None
+    for name in TEXTURES:
+        fpath = f"{dirname}/{fname}_{G}grid_{type}_{name}_mesh{idx:02d}.obj"
+        meshio.write_obj(fpath, verts, faces, colors=baked[name].cpu().numpy(), normals=normals)
+    return fpath
+
+
+def extract(dirname, fname, conf, verts, faces, train=False):
+    """`extract` (extract_by_mc.py:263-288) without its marching-cubes and trimming steps: the environment map, then the
+    raw mesh `verts`, `faces` with its six textures.  Returns the last mesh path."""
+    extract_environment_map(dirname, conf)
+    return save_attributed_mesh(dirname, fname, verts, faces, conf, train, "raw", 0)

@@ -112,6 +112,11 @@ SIGS = {
     "sparse_rows_zero_if_dropped": "qipl",
     "mlp_small_affine": "lpiipiiippi",
     "generate_raydir_camloc": "iixxqpipp",
+    # N raw_imp raw_bc raw_rough raw_spec ci cs act_imp beta_imp remap lower_bound spec_scale textures[6] std_max
+    "bake_head": "lppppiiififfPq",
+    "bake_scale": "lppq",
+    "envmap_directions": "ip",
+    "envmap_quantize": "iiippix",
     "solver_adam_begin": "xffqq",
     # n w g m v alpha_t beta1 beta2 eps decay zero_grad state
     "solver_adam": "lppppfffffix",
