@@ -30,8 +30,8 @@ from torch.autograd import Function
 
 from . import lib
 from .grid_feature import _core
-from .mlp import _launch, _packed, _Strided, amax_slots, blocked_layout, chain_workspace, engine_state, require_engine, colsum, grad_target, pb, wgrad, wgrad_group
-
+from .mlp import (ACCUM_Y, BLOCKED, ChainCall, _launch_chain, _packed, _Strided, amax_slots, bias_targets, blocked_layout, chain_workspace,
+                  engine_state, require_engine, colsum, grad_target, pb, reverse_chain, wgrad, wgrad_group)
 
 
 TRI_FUSED_MAX_POINTS = 16384      # ndjir_triplaneline_query_encode pays below this many points (see GeometricMain.forward)
@@ -54,10 +54,6 @@ def _ones(P, dev):
             _ONES.clear()
         t = _ONES[(P, dev)] = torch.ones((P, 1), device=dev, dtype=torch.float32)
     return t
-
-
-def _flops(P, Ks, Ns):
-    return 2.0 * P * sum(k * n for k, n in zip(Ks, Ns))
 
 
 def _sdf_col(W):
@@ -134,45 +130,22 @@ class GeometricMain(Function):
         am, sm = amax_slots(dev, L), amax_slots(dev, L)
         # every hidden tensor of the node (A_1.., s, g-bar_1.., extras, deltas) point-blocked where the 128-point-tile kernel runs
         blk = blocked_layout(P, [a.shape[1] for a in A[1:]], xf.is_cuda)
-        fl = 8 if blk else 0
-        _launch("chain_fwd", _flops(P, Ks, Ns), "mlp_chain", 0, P, e, K0, K0, L, [_packed(w, False) for w in W],
-                [t.detach() for t in b], Ks, Ns, [None] * L, A[1:] + [None], [a.shape[1] for a in A[1:]] + [0],
-                [None] * L, y, ldz, fl, 1, beta, skip_at, scale, 0, None, 0, None, None,
-                [am[j + 1:j + 2] for j in range(L - 1)] + [None], am[0:1],
-                shape=f"{P}:geo {K0}-" + "-".join(map(str, Ns)))
+        fl = BLOCKED if blk else 0
+        _launch_chain(ChainCall(0, P, e, K0, K0, L, [_packed(w, False) for w in W], [t.detach() for t in b], Ks, Ns,
+                                side_out=A[1:] + [None], ld_side=[a.shape[1] for a in A[1:]] + [0], Y=y, ldy=ldz, accum_y=fl,
+                                beta=beta, skip_layer=skip_at, skip_scale=scale,
+                                side_amax=[am[j + 1:j + 2] for j in range(L - 1)] + [None], x_amax=am[0:1],
+                                kind="chain_fwd", shape=f"{P}:geo {K0}-" + "-".join(map(str, Ns))))
 
         # ---- sdf chain: backward chain seeded with d(sdf) = 1, first step = column 0 of the last layer ----
         ones = _ones(P, dev)
-        s = [None] * L                                     # s[j] = d sdf / d z_j, j < L-1
-        s_store = [None] * L
-        Wp, bK, bN, side_in, side_out, ld, side_am = [], [], [], [], [], [], []
-        bskip, split = -1, 0
-        for i in range(L):
-            j = L - 1 - i
-            Wj = _sdf_col(W[j]) if j == L - 1 else W[j]
-            Wp.append(_packed(Wj, True))
-            bK.append(Wj.shape[1])
-            bN.append(Wj.shape[0])
-            if i < L - 1:
-                below = j - 1
-                buf = torch.empty((P, A[j].shape[1]), device=dev, dtype=torch.float32)
-                s_store[below] = buf
-                s[below] = buf[:, :Ns[below]]
-                side_in.append(A[j])
-                side_out.append(buf)
-                side_am.append(sm[below:below + 1])
-                ld.append(A[j].shape[1])
-                if below == skip_at:
-                    bskip, split = i, Ns[below]
-            else:
-                side_in.append(None)
-                side_out.append(None)
-                side_am.append(None)
-                ld.append(0)
+        # s[j] = d sdf / d z_j, j < L-1: the leading columns of s_store[j], which has the width of A[j + 1]
+        lists, s, _, bskip, split = reverse_chain(A, W[:-1] + [_sdf_col(W[-1])], L, skip_at, None, sm)
+        s_store = lists["side_out"][L - 2::-1] + [None]
         g0 = (torch.empty if bskip >= 0 else torch.zeros)((P, K0), device=dev, dtype=torch.float32)     # (skip layer: assigned, see mlp.FusedMLP.backward)
-        _launch("chain_bwd", _flops(P, bK, bN), "mlp_chain", 1, P, ones, 1, 1, L, Wp, [None] * L, bK, bN, side_in,
-                side_out, ld, [None] * L, g0, K0, (1 if bskip >= 0 else 0) | fl, 1, beta, bskip, scale, split,
-                g0 if bskip >= 0 else None, K0, None, None, side_am, None, shape=f"{P}:sdf 1-" + "-".join(map(str, bN)))
+        _launch_chain(ChainCall(1, P, ones, 1, 1, **lists, Y=g0, ldy=K0, accum_y=(ACCUM_Y if bskip >= 0 else 0) | fl, beta=beta,
+                                skip_layer=bskip, skip_scale=scale, skip_split=split, Xskip=g0 if bskip >= 0 else None, ld_xskip=K0,
+                                kind="chain_bwd", shape=f"{P}:sdf 1-" + "-".join(map(str, lists["Ns"]))))
 
         # ---- n = J_e(x)^T g_0 (one launch; it also completes Z and moves the sdf out of it) ----
         gqs, gos = [], []
@@ -189,7 +162,7 @@ class GeometricMain(Function):
         sdf = torch.empty((P, 1), device=dev, dtype=torch.float32)
         lib.call("geo_normal", P, M, e, K0, g0, K0, len(gqs), gqs, n, Z, ldz, D, sdf)
 
-        ctx.cfg = (M, skip_at, scale, min_, max_, L, tuple(x.shape), fam_names, bskip, split, ste, blk)
+        ctx.cfg = (M, skip_at, scale, min_, max_, L, tuple(x.shape), fam_names, ste, blk)
         ctx.engine = engine_state()
         ctx.btgt = [grad_target(t) for t in b]       # accumulate-in-place gradient buffers of the biases (mlp.set_grad_buffer)
         ctx.A, ctx.s_store, ctx.s = A, s_store, s
@@ -203,9 +176,9 @@ class GeometricMain(Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_sdf, g_feat, g_n, g_Z):
-        M, skip_at, scale, min_, max_, L, xshape, fam_names, bskip, split, ste, blk = ctx.cfg
+        M, skip_at, scale, min_, max_, L, xshape, fam_names, ste, blk = ctx.cfg
         require_engine(ctx.engine, blk)
-        fl = 8 if blk else 0
+        fl = BLOCKED if blk else 0
         saved = ctx.saved_tensors
         W = list(saved[:L])
         grids = list(saved[L:])
@@ -264,62 +237,34 @@ class GeometricMain(Function):
             gbar[0] = gb0
             # ---- tangent chain over layers 0..L-2 ----
             T = L - 1
-            side_in, side_in2, side_out, side_out2, ld, bg, side_am = [], [], [], [], [], [None] * T, []
-            for l in range(T):
-                wide = A[l + 1].shape[1]
-                gbar[l + 1] = torch.empty((P, wide), device=dev, dtype=torch.float32)
-                extras[l] = torch.empty((P, wide), device=dev, dtype=torch.float32)
-                side_in.append(A[l + 1])
-                side_in2.append(s_store[l])
-                side_out.append(gbar[l + 1])
-                side_out2.append(extras[l])
-                side_am.append(gm[l + 1:l + 2])
-                ld.append(wide)
+            for l in range(T):                       # g-bar_{l+1} and extra_l have the width of A_{l+1}
+                gbar[l + 1] = torch.empty_like(A[l + 1])
+                extras[l] = torch.empty_like(A[l + 1])
             col_last = torch.empty((Ns[L - 2],), device=dev, dtype=torch.float32)
-            bg[T - 1] = col_last
-            _launch("chain_tan", _flops(P, Ks[:T], Ns[:T]), "mlp_chain_ex", 2, P, gb0, K0, K0, T,
-                    [_packed(w, False) for w in W[:T]], [None] * T, Ks[:T], Ns[:T], side_in, side_out, ld, bg,
-                    None, 0, fl, 0, beta, skip_at, scale, 0, None, 0, side_in2, [None] * T, side_out2,
-                    None, 0, None, chain_workspace(dev, bg), side_am, gm[0:1], shape=f"{P}:tan {K0}-" + "-".join(map(str, Ns[:T])))
+            bg = [None] * (T - 1) + [col_last]
+            _launch_chain(ChainCall(2, P, gb0, K0, K0, T, [_packed(w, False) for w in W[:T]], [None] * T, Ks[:T], Ns[:T],
+                                    side_in=A[1:], side_out=gbar[1:], ld_side=[a.shape[1] for a in A[1:]], bgrad=bg, accum_y=fl,
+                                    has_output=0, beta=beta, skip_layer=skip_at, skip_scale=scale, side_in2=s_store[:T],
+                                    side_out2=extras[:T], workspace=chain_workspace(dev, bg),
+                                    side_amax=[gm[l + 1:l + 2] for l in range(T)], x_amax=gm[0:1], kind="chain_tan",
+                                    shape=f"{P}:tan {K0}-" + "-".join(map(str, Ns[:T]))))
 
         # ---- backward chain with the extra adjoints ----
         need_x = has_grid
         steps = L if need_x else L - 1
-        deltas = [None] * L
-        deltas[L - 1] = gy
-        bgrads = [None] * L
         nb = [ctx.needs_input_grad[2 + NG + L + j] for j in range(L)]
-        btgt = [t if nb[j] else None for j, t in enumerate(ctx.btgt)]
-        if any(nb[j] and btgt[j] is None for j in range(L)):
-            btgt = [None] * L                      # all of the net's biases accumulate in place, or none (one flag per chain)
-        bg_acc = 2 if any(t is not None for t in btgt) else 0
-        Wp, bK, bN, side_in, side_out, side_add, ld, bg, side_am = [], [], [], [], [], [], [], [], []
-        for i in range(steps):
-            j = L - 1 - i
-            Wp.append(_packed(W[j], True))
-            bK.append(Ns[j])
-            bN.append(Ks[j])
-            if i < L - 1:
-                below = j - 1
-                wide = A[j].shape[1]
-                dbuf = torch.empty((P, wide), device=dev, dtype=torch.float32)
-                deltas[below] = dbuf[:, :Ns[below]]
-                bgrads[below] = btgt[below] if btgt[below] is not None else torch.empty((Ns[below],), device=dev, dtype=torch.float32)
-                side_in.append(A[j])
-                side_out.append(dbuf)
-                side_add.append(extras[below])
-                side_am.append(dm[below:below + 1])
-                ld.append(wide)
-                bg.append(bgrads[below])
-            else:
-                side_in.append(None); side_out.append(None); side_add.append(None); ld.append(0); bg.append(None)
-                side_am.append(None)
+        btgt, bg_acc = bias_targets(ctx.btgt, nb)
+        lists, deltas, bgrads, bskip, split = reverse_chain(A, W, steps, skip_at, btgt, dm)
+        deltas[L - 1] = gy
+        side_add = (extras[L - 2::-1] + [None])[:steps]      # in step order: step i produces the delta of layer L-2-i
+        skip = bskip >= 0 and need_x
         gx = (torch.empty if bskip >= 0 else torch.zeros)((P, K0), device=dev, dtype=torch.float32) if need_x else None
         gb_last = btgt[L - 1] if btgt[L - 1] is not None else torch.empty((Ns[-1],), device=dev, dtype=torch.float32)     # bias gradient of the output layer
-        _launch("chain_bwd", _flops(P, bK, bN), "mlp_chain_ex", 1, P, gy, Ns[-1], Ns[-1], steps, Wp, [None] * steps, bK, bN,
-                side_in, side_out, ld, bg, gx, K0, (1 if (bskip >= 0 and need_x) else 0) | bg_acc | fl, 1 if need_x else 0, beta,
-                bskip, scale, split, gx if (bskip >= 0 and need_x) else None, K0, [None] * steps, side_add, [None] * steps,
-                None, 0, gb_last, chain_workspace(dev, bg + [gb_last]), side_am, dm[L - 1:L], shape=f"{P}:geo {Ns[-1]}-" + "-".join(map(str, bN)))
+        _launch_chain(ChainCall(1, P, gy, Ns[-1], Ns[-1], **lists, Y=gx, ldy=K0, accum_y=(ACCUM_Y if skip else 0) | bg_acc | fl,
+                                has_output=1 if need_x else 0, beta=beta, skip_layer=bskip, skip_scale=scale, skip_split=split,
+                                Xskip=gx if skip else None, ld_xskip=K0, side_add=side_add, in_bgrad=gb_last,
+                                workspace=chain_workspace(dev, lists["bgrad"] + [gb_last]), x_amax=dm[L - 1:L], kind="chain_bwd",
+                                shape=f"{P}:geo {Ns[-1]}-" + "-".join(map(str, lists["Ns"]))))
 
         for fam, fd, sa, C, c0, gdst, _ in enc:
             gxc = torch.empty((P, C), device=dev, dtype=torch.float32)

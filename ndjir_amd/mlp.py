@@ -10,9 +10,10 @@ Backward: one fused chain launch for the data path (delta of every layer + bias 
 gradient); weight gradients H^T delta by the split-P MFMA kernel of csrc/wgrad.hip.
 """
 import contextlib
+import dataclasses
+import operator
 import os
 import weakref
-
 
 import torch
 from torch.autograd import Function
@@ -88,15 +89,90 @@ def chain_kernel_symbol(mode, P, K0, Ks, Ns, has_output=True, skip_layer=-1, ski
     return buf.value.decode() if rc == 0 else f"ndjir chain (status {rc})"
 
 
-def _launch_symbol(name, args):
-    if name in ("mlp_chain", "mlp_chain_ex"):
-        return chain_kernel_symbol(args[0], args[1], args[4], args[8], args[9], bool(args[17]), args[19], args[21],
-                                   any(t is not None for t in args[13]) or (args[29 if name == "mlp_chain_ex" else 24] is not None))
-    if name == "mlp_wgrad_group":
-        return "ndjir::k_wgrad_group_wide + k_wgrad_group (+ k_wgrad_group_reduce)"
-    if name == "mlp_wgrad":
-        return "ndjir::k_wgrad3 / k_wgrad_narrow (+ split reduction)"
-    return "ndjir::" + name
+ACCUM_Y, ACCUM_BGRAD, DEFER_BGRAD, BLOCKED = 1, 2, 4, 8      # bits of `accum_y` (include/ndjir_hip.h, "ndjir_mlp_chain / _ex: `accum_y`")
+_EX_ONLY = ("side_in2", "side_add", "side_out2", "row_bias", "row_bias_div")
+
+
+@dataclasses.dataclass(slots=True)
+class ChainCall:
+    """One chain launch.  The launch fields are the parameters of ndjir_mlp_chain_ex (include/ndjir_hip.h) by name and in
+    order -- `args()` is the only place that turns them into a positional call --; `kind`, `flops` and `shape` are what the
+    profile records of the launch.  side_in / side_out / bgrad left at None are L null entries (ld_side: zeros)."""
+    mode: int
+    P: int
+    X: object
+    ldx: int
+    K0: int
+    L: int
+    Wp: list
+    bias: list
+    Ks: list
+    Ns: list
+    side_in: list = None
+    side_out: list = None
+    ld_side: list = None
+    bgrad: list = None
+    Y: object = None
+    ldy: int = 0
+    accum_y: int = 0
+    has_output: int = 1
+    beta: float = 100.0
+    skip_layer: int = -1
+    skip_scale: float = 1.0
+    skip_split: int = 0
+    Xskip: object = None
+    ld_xskip: int = 0
+    side_in2: list = None
+    side_add: list = None
+    side_out2: list = None
+    row_bias: object = None
+    row_bias_div: int = 0
+    in_bgrad: object = None
+    workspace: object = None
+    side_amax: list = None
+    x_amax: object = None
+    kind: str = "chain_fwd"
+    flops: float = None         # (default: 2 * in * out per layer and point)
+    shape: str = ""
+
+    def __post_init__(self):
+        if self.side_in is None:
+            self.side_in = [None] * self.L
+        if self.side_out is None:
+            self.side_out = [None] * self.L
+        if self.bgrad is None:
+            self.bgrad = [None] * self.L
+        if self.ld_side is None:
+            self.ld_side = [0] * self.L
+        if self.flops is None:
+            self.flops = 2.0 * self.P * sum(k * n for k, n in zip(self.Ks, self.Ns))
+
+    @property
+    def entry(self):
+        """The extended entry point for a tangent chain and for any launch that sets one of its own arguments."""
+        ex = self.mode == 2 or any(v is not None for v in (self.side_in2, self.side_add, self.side_out2, self.row_bias))
+        return "mlp_chain_ex" if ex else "mlp_chain"
+
+    def args(self):
+        """The arguments of `lib.call(self.entry, ...)`; the extended entry point takes its unset lists as L null entries."""
+        if self.entry == "mlp_chain":
+            return _PLAIN_ARGS(self)
+        a, i = _EX_ARGS(self), _EX_AT
+        return a[:i] + tuple(v or [None] * self.L for v in a[i:i + 3]) + a[i + 3:]
+
+
+_LAUNCH_FIELDS = tuple(f.name for f in dataclasses.fields(ChainCall))[:-3]
+_EX_ARGS, _EX_AT = operator.attrgetter(*_LAUNCH_FIELDS), _LAUNCH_FIELDS.index("side_in2")
+_PLAIN_ARGS = operator.attrgetter(*[n for n in _LAUNCH_FIELDS if n not in _EX_ONLY])
+
+
+def _chain_symbol(call):
+    return chain_kernel_symbol(call.mode, call.P, call.K0, call.Ks, call.Ns, bool(call.has_output), call.skip_layer,
+                               call.skip_split, any(t is not None for t in call.bgrad) or call.in_bgrad is not None)
+
+
+_SYMBOLS = {"mlp_wgrad_group": "ndjir::k_wgrad_group_wide + k_wgrad_group (+ k_wgrad_group_reduce)",
+            "mlp_wgrad": "ndjir::k_wgrad3 / k_wgrad_narrow (+ split reduction)"}      # (other launches: "ndjir::" + entry point)
 
 
 _BIAS_ARENA = {}       # device -> [tensor, next free float]: partial rows of deferred bias-gradient reductions of one step
@@ -119,26 +195,25 @@ def _bias_region(device, floats):
     return out
 
 
-def _defer_bias_reduction(name, args):
+def _defer_bias_reduction(call):
     """Inside `deferred_wgrads()`, a backward / tangent chain launch whose bias gradients ACCUMULATE into persistent buffers
     (`set_grad_buffer`) does not reduce its per-workgroup partial rows itself (one small launch per chain, 13 per step): it
     leaves them in a private region and the step's one reduction launch sums them with the weight-gradient slabs.
-    Returns the launch's arguments with the DEFER flag and the region in place, or None when the launch does not qualify."""
+    Returns a copy of the call with the DEFER flag and the region in place, or None when the launch does not qualify."""
     import ctypes
-    if _DEFERRED is None or name not in ("mlp_chain", "mlp_chain_ex") or int(args[0]) == 0 or not (int(args[16]) & 2):
+    if _DEFERRED is None or int(call.mode) == 0 or not (int(call.accum_y) & ACCUM_BGRAD):
         return None
     if get_math() != MATH_F16X3:
         return None
-    i_in = 29 if name == "mlp_chain_ex" else 24
-    bg, in_bg, L = args[13], args[i_in], int(args[5])
-    has_output = bool(args[17])
+    mode, P, K0, L, in_bg = int(call.mode), int(call.P), int(call.K0), int(call.L), call.in_bgrad
+    Ks, Ns = tuple(int(k) for k in call.Ks), tuple(int(n) for n in call.Ns)
+    has_output, skip, split = bool(call.has_output), int(call.skip_layer), int(call.skip_split)
     # the bias gradients the launch produces, in the order of its partial rows: layers (never an output layer), then the input
-    live = [(j, t) for j, t in enumerate(bg) if t is not None and not (has_output and j == L - 1)]
+    live = [(j, t) for j, t in enumerate(call.bgrad) if t is not None and not (has_output and j == L - 1)]
     if not live and in_bg is None:
         return None
     mask = sum(1 << j for j, _ in live)
-    key = (name, int(args[0]), int(args[1]), int(args[4]), tuple(int(k) for k in args[8]), tuple(int(n) for n in args[9]), has_output,
-           int(args[19]), int(args[21]), mask, in_bg is not None, get_tile_rows())
+    key = (call.entry, mode, P, K0, Ks, Ns, has_output, skip, split, mask, in_bg is not None, get_tile_rows())
     lay = _BIAS_LAYOUT.get(key)
     if lay is None:
         blocks, row = ctypes.c_int(0), ctypes.c_int(0)
@@ -147,8 +222,7 @@ def _defer_bias_reduction(name, args):
                       ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                       ctypes.POINTER(ctypes.c_int)]
         f.restype = ctypes.c_int
-        rc = f(int(args[0]), int(args[1]), int(args[4]), L, (ctypes.c_int * L)(*[int(k) for k in args[8]]),
-               (ctypes.c_int * L)(*[int(n) for n in args[9]]), 1 if has_output else 0, int(args[19]), int(args[21]), mask,
+        rc = f(mode, P, K0, L, (ctypes.c_int * L)(*Ks), (ctypes.c_int * L)(*Ns), 1 if has_output else 0, skip, split, mask,
                1 if in_bg is not None else 0, ctypes.byref(blocks), ctypes.byref(row))
         lay = _BIAS_LAYOUT[key] = (blocks.value, row.value) if rc == 0 else None
         if len(_BIAS_LAYOUT) > 4096:
@@ -158,21 +232,18 @@ def _defer_bias_reduction(name, args):
     # (a destination may be deferred more than once per step -- a net that runs twice, the geometric net's first-order pass:
     # the grouped launch puts outputs that touch the same memory into different generations, one reduction launch each)
     blocks, row = lay
-    x = args[2]
+    x = call.X
     region = _bias_region((x if torch.is_tensor(x) else x.t).device, blocks * row)
     off = 0
     for j, t in live:
-        n = int(args[9][j])
+        n = int(call.Ns[j])
         _DEFERRED_BIAS.append((t, region[off:], n, blocks, row))
         off += n
     if in_bg is not None:
-        _DEFERRED_BIAS.append((in_bg, region[off:], int(args[4]), blocks, row))
-        off += int(args[4])
+        _DEFERRED_BIAS.append((in_bg, region[off:], K0, blocks, row))
+        off += K0
     assert off <= row < off + 4, (off, row)          # (the launchers pad a partial row to a multiple of 4 floats)
-    args = list(args)
-    args[16] = int(args[16]) | 4
-    args[i_in + 1] = region
-    return tuple(args)
+    return dataclasses.replace(call, accum_y=int(call.accum_y) | DEFER_BGRAD, workspace=region)
 
 
 _GROUP = None          # inside `chain_group()`: the chain launches recorded so far
@@ -205,11 +276,10 @@ def _width_class(W):
     return 0 if (max(hidden) if hidden else 0) > 128 else 1
 
 
-def _group_class(args):
+def _group_class(call):
     """Nets that can share a launch have hidden layers of the same width class (the kernel's row-blocks-per-wave choice)."""
-    Ns, L, has_out = args[9], int(args[5]), bool(args[17])
-    hidden = [int(n) for j, n in enumerate(Ns) if not (has_out and j == L - 1)]
-    return (int(args[0]), int(args[1]), (max(hidden) if hidden else 0) <= 128)
+    hidden = [int(n) for j, n in enumerate(call.Ns) if not (call.has_output and j == int(call.L) - 1)]
+    return (int(call.mode), int(call.P), (max(hidden) if hidden else 0) <= 128)
 
 
 def _flush_chain_group(calls):
@@ -218,71 +288,69 @@ def _flush_chain_group(calls):
     i = 0
     while i < len(calls):
         j = i + 1
-        key = _group_class(calls[i][3])
-        while j < len(calls) and j - i < CHAIN_GROUP_MAX and _group_class(calls[j][3]) == key:
+        key = _group_class(calls[i])
+        while j < len(calls) and j - i < CHAIN_GROUP_MAX and _group_class(calls[j]) == key:
             j += 1
         run = calls[i:j]
         i = j
         if len(run) == 1:
-            _launch_now(*run[0])
+            _launch_chain_now(run[0])
             continue
         so = lib.load()
         so.ndjir_mlp_chain_group_end.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
         n_launch = ctypes.c_int(0)
         stream = torch.cuda.current_stream().cuda_stream
-        if PROFILE is None:
-            rc = so.ndjir_mlp_chain_group_begin()
-            if rc != 0:
-                raise lib.NdjirHipError(f"ndjir_mlp_chain_group_begin failed with status {rc}")
-            try:
-                for kind, flops, name, args, shape in run:
-                    lib.call(name, *args)
-            finally:
-                rc = so.ndjir_mlp_chain_group_end(ctypes.c_void_p(stream), ctypes.byref(n_launch))
-            if rc != 0:
-                raise lib.NdjirHipError(f"ndjir_mlp_chain_group_end failed with status {rc}")
-            continue
         # profiling: one entry per group launch (the sum of its nets' algorithmic work; the input tile is counted once per
         # net -- every net stages it again, from L2)
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
+        if PROFILE is not None:
+            e0 = torch.cuda.Event(enable_timing=True)
+            e1 = torch.cuda.Event(enable_timing=True)
+            e0.record()
         rc = so.ndjir_mlp_chain_group_begin()
         if rc != 0:
             raise lib.NdjirHipError(f"ndjir_mlp_chain_group_begin failed with status {rc}")
         try:
-            for kind, flops, name, args, shape in run:
-                lib.call(name, *args)
+            for call in run:
+                lib.call(call.entry, *call.args())
         finally:
             rc = so.ndjir_mlp_chain_group_end(ctypes.c_void_p(stream), ctypes.byref(n_launch))
-        e1.record()
+        if PROFILE is not None:
+            e1.record()
         if rc != 0:
             raise lib.NdjirHipError(f"ndjir_mlp_chain_group_end failed with status {rc}")
-        kind, _, name, args, _ = run[0]
-        sym = _launch_symbol(name, args)
-        if n_launch.value == 1:
-            sym = sym.replace("k_chainw<", "k_chainw_nets<")      # (the group instantiation of the same kernel body)
-        PROFILE.append((kind, sum(r[1] for r in run), e0, e1, " + ".join(r[4] for r in run),
-                        sum(_launch_bytes(r[2], r[3]) for r in run), sym, max(1, n_launch.value)))
+        if PROFILE is not None:
+            sym = _chain_symbol(run[0])
+            if n_launch.value == 1:
+                sym = sym.replace("k_chainw<", "k_chainw_nets<")      # (the group instantiation of the same kernel body)
+            PROFILE.append((run[0].kind, sum(c.flops for c in run), e0, e1, " + ".join(c.shape for c in run),
+                            sum(_chain_bytes(c) for c in run), sym, max(1, n_launch.value)))
+
+
+def _launch_chain(call):
+    """Launch a `ChainCall`: now, or at the end of the enclosing `chain_group()`."""
+    call = _defer_bias_reduction(call) or call
+    if _GROUP is not None:
+        _GROUP.append(call)
+        return
+    _launch_chain_now(call)
+
+
+def _launch_chain_now(call):
+    kind = call.kind
+    if PROFILE is not None and not os.environ.get("NDJIR_MLP_TILE") and (int(call.P) + 63) // 64 < 256:
+        kind += "_t32"            # small launch: the library picks 32-point tiles (a different kernel instantiation)
+    _launch_now(kind, call.flops, call.entry, call.args(), call.shape, call)
 
 
 def _launch(kind, flops, name, *args, shape=""):
-    deferred = _defer_bias_reduction(name, args)
-    if deferred is not None:
-        args = deferred
-    if _GROUP is not None and name in ("mlp_chain", "mlp_chain_ex"):
-        _GROUP.append((kind, flops, name, args, shape))
-        return
     _launch_now(kind, flops, name, args, shape)
 
 
-def _launch_now(kind, flops, name, args, shape):
+def _launch_now(kind, flops, name, args, shape, chain=None):
     if PROFILE is None:
         lib.call(name, *args)
         return
-    if kind.startswith("chain") and not os.environ.get("NDJIR_MLP_TILE") and (int(args[1]) + 63) // 64 < 256:
-        kind += "_t32"            # small launch: the library picks 32-point tiles (a different kernel instantiation)
-    sym = _launch_symbol(name, args)
+    sym = _chain_symbol(chain) if chain is not None else _SYMBOLS.get(name, "ndjir::" + name)
     e0 = torch.cuda.Event(enable_timing=True)
     e1 = torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -294,24 +362,26 @@ def _launch_now(kind, flops, name, args, shape):
         n, m = int(args[0]), int(args[9])
         n_kernels = max(1, int(lib.load().ndjir_mlp_wgrad_group_launches(
             n, (ctypes.c_longlong * n)(*[int(p) for p in args[5]]), (ctypes.c_int * n)(*[int(o) for o in args[8]]), m)))
-    PROFILE.append((kind, flops, e0, e1, shape, _launch_bytes(name, args), sym, n_kernels))
+    nbytes = _chain_bytes(chain) if chain is not None else _launch_bytes(name, args)
+    PROFILE.append((kind, flops, e0, e1, shape, nbytes, sym, n_kernels))
+
+
+def _chain_bytes(call):
+    """Algorithmic HBM bytes of a chain launch (profiling only): every (P, width) fp32 tensor the launch has to read or write
+    once -- chain input, output (twice when accumulated into), stored activations / deltas / adjoints of the hidden layers --;
+    the packed weights (L2-resident, < 1 MB per net) are not counted."""
+    P = int(call.P)
+    n = P * int(call.K0)
+    for lst in (call.side_in, call.side_out, call.side_in2, call.side_add, call.side_out2):
+        if lst is not None:
+            n += sum(P * int(call.ld_side[j]) for j, t in enumerate(lst) if t is not None)
+    if call.Y is not None and int(call.has_output):
+        n += P * int(call.Ns[int(call.L) - 1]) * (2 if int(call.accum_y) & ACCUM_Y else 1)
+    return 4.0 * n
 
 
 def _launch_bytes(name, args):
-    """Algorithmic HBM bytes of a launch (profiling only): every (P, width) fp32 tensor the launch has to read or write once
-    -- chain input, output (twice when accumulated into), stored activations / deltas / adjoints of the hidden layers --;
-    the packed weights (L2-resident, < 1 MB per net) are not counted.  wgrad: both operands + the gradient."""
-    if name in ("mlp_chain", "mlp_chain_ex"):
-        P, K0, L = int(args[1]), int(args[4]), int(args[5])
-        Ns, ld = args[9], args[12]
-        n = P * K0
-        lists = [args[10], args[11]] + ([args[24], args[25], args[26]] if name == "mlp_chain_ex" else [])
-        for lst in lists:
-            if lst is not None:
-                n += sum(P * int(ld[j]) for j, t in enumerate(lst) if t is not None)
-        if args[14] is not None and int(args[17]):
-            n += P * int(Ns[L - 1]) * (2 if int(args[16]) & 1 else 1)
-        return 4.0 * n
+    """Algorithmic HBM bytes of a weight-gradient / column-sum launch (profiling only): both operands + the gradient."""
     if name == "mlp_wgrad":
         K, N, P = int(args[4]), int(args[5]), int(args[6])
         return 4.0 * (P * (K + N) + K * N * (2 if int(args[8]) else 1))
@@ -669,8 +739,8 @@ def blocked_layout(P, hidden_widths, is_cuda=True):
 
 
 def engine_state():
-    """(arithmetic engine, forced tile height) of the MLP library: process-wide settings (`set_math`, `set_tile_rows`) that
-    decide the layout of the hidden tensors a forward pass stores."""
+    """(arithmetic engine, forced tile height, chain-pipeline mask) of the MLP library: process-wide settings (`set_math`,
+    `set_tile_rows`, `set_chain_pipeline`) that decide the layout of the hidden tensors a forward pass stores."""
     return (get_math(), get_tile_rows(), get_chain_pipeline())
 
 
@@ -679,8 +749,9 @@ def require_engine(saved, blocked):
     readable by the engine and tile height that wrote them, so a switch between the two passes (or under a live captured
     graph) is refused here, by name, instead of surfacing as NDJIR_ERR_UNSUPPORTED from a kernel launch."""
     if blocked and saved is not None and saved != engine_state():
-        raise RuntimeError(f"ndjir_amd.mlp: the MLP engine changed between forward and backward ((math, tile_rows) {saved} -> "
-                           f"{engine_state()}); set_math / set_tile_rows must not be called while a forward pass's graph "
+        raise RuntimeError(f"ndjir_amd.mlp: the MLP engine changed between forward and backward ((math, tile_rows, "
+                           f"chain_pipeline) {saved} -> {engine_state()}); set_math / set_tile_rows / set_chain_pipeline must "
+                           f"not be called while a forward pass's graph "
                            f"(autograd or captured HIP graph) is alive")
 
 
@@ -703,7 +774,7 @@ def chain_forward(x, weights, biases, beta=100.0, skip_layer=-1, skip_scale=1.0,
     consecutive rows.  out = (tensor or pointer wrapper, row stride): where y goes instead of a fresh (P, N_last) tensor.
     blocked: the stored activations are written point-blocked (`PB`; `blocked_layout` says when that pays)."""
     P, ldx = x.shape
-    blk = 8 if (blocked and keep_hidden) else 0
+    blk = BLOCKED if (blocked and keep_hidden) else 0
     K0 = ldx if K0 is None else int(K0)
     L = len(weights)
     Ks, Ns, Wp, hidden = [], [], [], []
@@ -722,22 +793,17 @@ def chain_forward(x, weights, biases, beta=100.0, skip_layer=-1, skip_scale=1.0,
         y, ldy = out
     side_out = (hidden + [None]) if keep_hidden else [None] * L
     ld_side = [h.shape[1] if h is not None else 0 for h in side_out]
-    flops = 2.0 * P * sum(k * n for k, n in zip(Ks, Ns))
     bl = [b.detach() if b is not None else None for b in biases]
     am = amax_slots(x.device, L) if keep_hidden else None
     side_am = [_slot(am, j + 1) if (keep_hidden and j < L - 1) else None for j in range(L)]
-    if row_bias is None:
-        _launch("chain_fwd", flops, "mlp_chain", 0, P, x, ldx, K0, L, Wp, bl,
-                Ks, Ns, [None] * L, side_out, ld_side, [None] * L, y, ldy, blk, 1, float(beta),
-                int(skip_layer), float(skip_scale), 0, None, 0, None, None, side_am, _slot(am, 0),
-                shape=f"{P}:{K0}-" + "-".join(map(str, Ns)))
-    else:
+    call = ChainCall(0, P, x, ldx, K0, L, Wp, bl, Ks, Ns, side_out=side_out, ld_side=ld_side, Y=y, ldy=ldy, accum_y=blk,
+                     beta=float(beta), skip_layer=int(skip_layer), skip_scale=float(skip_scale), side_amax=side_am,
+                     x_amax=_slot(am, 0), kind="chain_fwd", shape=f"{P}:{K0}-" + "-".join(map(str, Ns)))
+    if row_bias is not None:
         assert P % row_bias_div == 0 and tuple(row_bias.shape) == (P // row_bias_div, Ns[0])
-        _launch("chain_fwd", flops, "mlp_chain_ex", 0, P, x, ldx, K0, L, Wp, bl,
-                Ks, Ns, [None] * L, side_out, ld_side, [None] * L, y, ldy, blk, 1, float(beta),
-                int(skip_layer), float(skip_scale), 0, None, 0, [None] * L, [None] * L, [None] * L,
-                row_bias.detach().contiguous(), int(row_bias_div), None, None, side_am, _slot(am, 0),
-                shape=f"{P}:{K0}(+rows/{row_bias_div})-" + "-".join(map(str, Ns)))
+        call.row_bias, call.row_bias_div = row_bias.detach().contiguous(), int(row_bias_div)
+        call.shape = f"{P}:{K0}(+rows/{row_bias_div})-" + "-".join(map(str, Ns))
+    _launch_chain(call)
     return y, hidden, am
 
 
@@ -999,6 +1065,51 @@ def _col_tail(W):
     return hit[2]
 
 
+def bias_targets(targets, needed):
+    """Accumulate-in-place destinations (`set_grad_buffer`) of a net's bias gradients: targets[j] where layer j's gradient is
+    needed, for all of those layers or for none -- a chain launch has one ACCUM_BGRAD flag.  Returns the list and that flag."""
+    btgt = [t if need else None for t, need in zip(targets, needed)]
+    if any(need and t is None for t, need in zip(btgt, needed)):
+        btgt = [None] * len(btgt)
+    return btgt, (ACCUM_BGRAD if any(t is not None for t in btgt) else 0)
+
+
+def reverse_chain(A, W, steps, skip_layer=-1, btgt=None, amax=None):
+    """Per-layer arguments of a backward-direction chain over layers L-1 .. L-steps of a net: weights W, A[j] = the stored input
+    of layer j.  Step i applies W[L-1-i]^T; unless that is the net's first layer it reads A[j] and writes the delta of the
+    layer below to a fresh buffer of A[j]'s width and row stride (deltas[below] = its leading columns: all of them, except
+    below a skip connection, where A[j] also holds the net's input).  btgt (None: no bias gradients) = `bias_targets`, a None
+    entry gets a fresh vector; amax: slots for the deltas' recorded maxima.
+    Returns (keyword arguments of `ChainCall`, deltas, bgrads, step whose output is the skip layer's delta or -1, its width)."""
+    L, P, dev = len(W), A[0].shape[0], A[0].device
+    Wp, Ks, Ns, side_in, side_out, ld_side, bgrad, side_amax = ([] for _ in range(8))
+    deltas, bgrads = [None] * L, [None] * L
+    skip_step, split = -1, 0
+    for i in range(steps):
+        j = L - 1 - i
+        below = j - 1
+        Wp.append(_packed(W[j], True))
+        Ks.append(W[j].shape[1])
+        Ns.append(W[j].shape[0])
+        buf = bg = None
+        if below >= 0:
+            N = W[below].shape[1]
+            buf = torch.empty((P, A[j].shape[1]), device=dev, dtype=torch.float32)
+            deltas[below] = buf if N == buf.shape[1] else buf[:, :N]
+            if btgt is not None:
+                bg = bgrads[below] = btgt[below] if btgt[below] is not None else torch.empty((N,), device=dev, dtype=torch.float32)
+            if below == skip_layer:
+                skip_step, split = i, N
+        side_in.append(A[j] if below >= 0 else None)
+        side_out.append(buf)
+        ld_side.append(A[j].shape[1] if below >= 0 else 0)
+        bgrad.append(bg)
+        side_amax.append(_slot(amax, below) if below >= 0 else None)
+    lists = dict(L=steps, Wp=Wp, bias=[None] * steps, Ks=Ks, Ns=Ns, side_in=side_in, side_out=side_out, ld_side=ld_side,
+                 bgrad=bgrad, side_amax=side_amax)
+    return lists, deltas, bgrads, skip_step, split
+
+
 class FusedMLP(Function):
     @staticmethod
     def forward(ctx, x, row_bias, row_bias_div, beta, skip_layer, skip_scale, pack, *params):
@@ -1063,54 +1174,13 @@ class FusedMLP(Function):
             gy2 = gy.reshape(P, -1).contiguous()
         # backward chain: step i applies W_{L-1-i}^T
         steps = L if need_x else L - 1
-        deltas = [None] * L                  # deltas[j] = dL/dz_j
-        deltas[L - 1] = gy2
-        bgrads = [None] * L
-        gx = None
-        gb_last = None
+        gx = gb_last = None
         dm = amax_slots(x2.device, L)        # recorded maxima of deltas[j]; slot L-1 = the chain input gy2
         have_dm = steps > 0
-        # accumulate-in-place gradient buffers (set_grad_buffer): all of the net's biases or none (one flag per chain launch)
-        btgt = [t if ctx.needs_input_grad[7 + L + j] else None for j, t in enumerate(ctx.btgt)]
-        if any(ctx.needs_input_grad[7 + L + j] and btgt[j] is None for j in range(L)):
-            btgt = [None] * L
-        bg_acc = 2 if any(t is not None for t in btgt) else 0
+        btgt, bg_acc = bias_targets(ctx.btgt, ctx.needs_input_grad[7 + L:7 + 2 * L])
+        lists, deltas, bgrads, bwd_skip, split = reverse_chain(A, W, steps, skip_layer, btgt, dm)
+        deltas[L - 1] = gy2                  # deltas[j] = dL/dz_j
         if steps > 0:
-            Wp, Ks, Ns, side_in, side_out, ld_side, bg, side_am = [], [], [], [], [], [], [], []
-            bwd_skip, split = -1, 0
-            for i in range(steps):
-                j = L - 1 - i
-                Wp.append(_packed(W[j], True))
-                Ks.append(W[j].shape[1])
-                Ns.append(W[j].shape[0])
-                if i < L - 1:
-                    below = j - 1                       # layer whose delta this step produces
-                    width = W[below].shape[1]
-                    deltas[below] = torch.empty((P, width), device=x2.device, dtype=torch.float32)
-                    bgrads[below] = (btgt[below] if btgt[below] is not None
-                                     else torch.empty((width,), device=x2.device, dtype=torch.float32))
-                    side_in.append(A[j])
-                    side_out.append(deltas[below])
-                    side_am.append(_slot(dm, below))
-                    ld_side.append(A[j].shape[1])
-                    bg.append(bgrads[below])
-                    if below == skip_layer:
-                        bwd_skip, split = i, width
-                        # delta store of the skip layer shares the activation's row stride only if equal
-                        ld_side[-1] = A[j].shape[1]
-                else:
-                    side_in.append(None)
-                    side_out.append(None)
-                    side_am.append(None)
-                    ld_side.append(0)
-                    bg.append(None)
-            if bwd_skip >= 0:
-                # side_in (stride = concatenated width) and side_out (stride = split) differ: give the
-                # delta buffer the activation's stride and slice afterwards
-                j = L - 1 - bwd_skip
-                wide = torch.empty((P, A[j].shape[1]), device=x2.device, dtype=torch.float32)
-                side_out[bwd_skip] = wide
-                deltas[skip_layer] = wide[:, :split]
             ldg = K0
             if need_x:
                 if bwd_skip >= 0:
@@ -1121,7 +1191,6 @@ class FusedMLP(Function):
                     # rows padded to 16 bytes: the output layer then stores float4 (K0 = 259, 262, 301 ...)
                     ldg = (K0 + 3) // 4 * 4
                     gx = torch.empty((P, ldg), device=x2.device, dtype=torch.float32)[:, :K0]
-            flops = 2.0 * P * sum(k * n for k, n in zip(Ks, Ns))
             if need_w and ctx.needs_input_grad[7 + 2 * L - 1]:
                 # bias gradient of the output layer = column sums of dL/dY: accumulated by the chain's input load
                 if btgt[L - 1] is not None:
@@ -1131,12 +1200,13 @@ class FusedMLP(Function):
                     gb_last = gb_full[1:]
                 else:
                     gb_last = torch.empty((gy2.shape[1],), device=x2.device, dtype=torch.float32)
-            _launch("chain_bwd", flops, "mlp_chain", 1, P, _Strided(gy2), gy2.stride(0), gy2.shape[1], steps, Wp, [None] * steps, Ks, Ns,
-                     side_in, side_out, ld_side, bg, _Strided(gx) if gx is not None else None, ldg,
-                     (1 if bwd_skip >= 0 else 0) | bg_acc | (8 if blk else 0), 1 if need_x else 0,
-                     float(beta), int(bwd_skip), float(skip_scale), int(split),
-                     gx if bwd_skip >= 0 else None, K0, gb_last, chain_workspace(x2.device, bg + [gb_last]),
-                     side_am, _slot(dm, L - 1), shape=f"{P}:{gy2.shape[1]}-" + "-".join(map(str, Ns)))
+            _launch_chain(ChainCall(
+                1, P, _Strided(gy2), gy2.stride(0), gy2.shape[1], **lists, Y=_Strided(gx) if gx is not None else None, ldy=ldg,
+                accum_y=(ACCUM_Y if bwd_skip >= 0 else 0) | bg_acc | (BLOCKED if blk else 0), has_output=1 if need_x else 0,
+                beta=float(beta), skip_layer=int(bwd_skip), skip_scale=float(skip_scale), skip_split=int(split),
+                Xskip=gx if bwd_skip >= 0 else None, ld_xskip=K0, in_bgrad=gb_last,
+                workspace=chain_workspace(x2.device, lists["bgrad"] + [gb_last]), x_amax=_slot(dm, L - 1), kind="chain_bwd",
+                shape=f"{P}:{gy2.shape[1]}-" + "-".join(map(str, lists["Ns"]))))
         gW = [None] * L
         gb = [None] * L
         if need_w:
@@ -1297,37 +1367,20 @@ class MultiMLP(Function):
                 nb = ctx.needs_input_grad[wo + L:wo + 2 * L]
                 gy2 = gy.reshape(P, -1).contiguous()
                 steps = L if need_x else L - 1
-                deltas, bgrads = [None] * L, [None] * L
-                deltas[L - 1] = gy2
                 gb_last = None
-                # accumulate-in-place gradient buffers (set_grad_buffer): all of the net's biases or none (one flag per chain)
-                btgt = [t if nb[j] else None for j, t in enumerate(ctx.btgts[n])]
-                if any(nb[j] and btgt[j] is None for j in range(L)):
-                    btgt = [None] * L
-                bg_acc = 2 if any(t is not None for t in btgt) else 0
+                btgt, bg_acc = bias_targets(ctx.btgts[n], nb)
                 dm = amax_slots(dev, L) if steps > 0 else None
+                lists, deltas, bgrads, _, _ = reverse_chain(A, W, steps, -1, btgt, dm)
+                deltas[L - 1] = gy2
                 if steps > 0:
-                    Wp, Ks, Ns, side_in, side_out, ld_side, bg, side_am = [], [], [], [], [], [], [], []
-                    for i in range(steps):
-                        j = L - 1 - i
-                        Wp.append(_packed(W[j], True))
-                        Ks.append(W[j].shape[1])
-                        Ns.append(W[j].shape[0])
-                        if i < L - 1:
-                            width = W[j - 1].shape[1]
-                            deltas[j - 1] = torch.empty((P, width), device=dev, dtype=torch.float32)
-                            bgrads[j - 1] = btgt[j - 1] if btgt[j - 1] is not None else torch.empty((width,), device=dev, dtype=torch.float32)
-                            side_in.append(A[j]); side_out.append(deltas[j - 1]); ld_side.append(A[j].shape[1]); bg.append(bgrads[j - 1])
-                            side_am.append(_slot(dm, j - 1))
-                        else:
-                            side_in.append(None); side_out.append(None); ld_side.append(0); bg.append(None); side_am.append(None)
                     if any(nW) and nb[L - 1]:
                         gb_last = btgt[L - 1] if btgt[L - 1] is not None else torch.empty((gy2.shape[1],), device=dev, dtype=torch.float32)
-                    flops = 2.0 * P * sum(k * m for k, m in zip(Ks, Ns))
-                    _launch("chain_bwd", flops, "mlp_chain", 1, P, gy2, gy2.shape[1], gy2.shape[1], steps, Wp, [None] * steps, Ks, Ns,
-                            side_in, side_out, ld_side, bg, _Strided(gx) if gx is not None else None, ldg,
-                            (0 if first else 1) | bg_acc | (8 if blk else 0), 1 if need_x else 0, float(beta), -1, 1.0, 0, None, K0, gb_last,
-                            chain_workspace(dev, bg + [gb_last]), side_am, _slot(dm, L - 1), shape=f"{P}:{gy2.shape[1]}-" + "-".join(map(str, Ns)) + ("" if first else " (+=)"))
+                    _launch_chain(ChainCall(
+                        1, P, gy2, gy2.shape[1], gy2.shape[1], **lists, Y=_Strided(gx) if gx is not None else None, ldy=ldg,
+                        accum_y=(0 if first else ACCUM_Y) | bg_acc | (BLOCKED if blk else 0), has_output=1 if need_x else 0,
+                        beta=float(beta), ld_xskip=K0, in_bgrad=gb_last, workspace=chain_workspace(dev, lists["bgrad"] + [gb_last]),
+                        x_amax=_slot(dm, L - 1), kind="chain_bwd",
+                        shape=f"{P}:{gy2.shape[1]}-" + "-".join(map(str, lists["Ns"])) + ("" if first else " (+=)")))
                     first = False
                 state.append((n, A, W, am, dm, deltas, bgrads, btgt, gb_last, gy2, nW, nb, blk))
         # phase 2: what reads the chains' outputs -- row-term gradients, weight gradients, bias gradients
@@ -1391,9 +1444,8 @@ def _mm(x2, W, transpose, bias=None):
         _launch("affine_small", 2.0 * P_ * K * N, "mlp_small_affine", P_, x2, x2.shape[1], K, _Strided(W.detach()), W.stride(0), N,
                 int(bool(transpose)), bias.detach() if bias is not None else None, y, N, shape=f"{P_}:{K}-{N}")
         return y
-    _launch("chain_fwd", 2.0 * P_ * K * N, "mlp_chain", 0, P_, x2, x2.shape[1], K, 1, [_packed(W, bool(transpose))],
-            [bias.detach() if bias is not None else None], [K], [N], [None], [None], [0], [None], y, N, 0, 1, 100.0, -1, 1.0, 0,
-            None, 0, None, None, None, None, shape=f"{P_}:{K}-{N}")
+    _launch_chain(ChainCall(0, P_, x2, x2.shape[1], K, 1, [_packed(W, bool(transpose))], [bias.detach() if bias is not None else None],
+                            [K], [N], Y=y, ldy=N, kind="chain_fwd", shape=f"{P_}:{K}-{N}"))
     return y
 
 
