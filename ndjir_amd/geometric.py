@@ -30,7 +30,7 @@ from torch.autograd import Function
 
 from . import lib
 from .grid_feature import _core
-from .mlp import (ACCUM_Y, BLOCKED, ChainCall, _launch_chain, _packed, _Strided, amax_slots, bias_targets, blocked_layout, chain_workspace,
+from .mlp import (ACCUM_Y, BLOCKED, ChainCall, WgradJob, WgradSource, _launch_chain, _packed, _Strided, amax_slots, bias_targets, blocked_layout, chain_workspace,
                   engine_state, require_engine, colsum, grad_target, pb, reverse_chain, wgrad, wgrad_group)
 
 
@@ -280,10 +280,10 @@ class GeometricMain(Function):
                 dst = wt if wt is not None else torch.empty(tuple(W[j].shape), device=dev, dtype=torch.float32)
                 if wt is None:
                     gW[j] = dst
-                src = [(pb(A[j], blk and j > 0), pb(deltas[j], blk and j < L - 1), am[j:j + 1], dm[j:j + 1])]
+                src = [WgradSource(pb(A[j], blk and j > 0), pb(deltas[j], blk and j < L - 1), am[j:j + 1], dm[j:j + 1])]
                 if nbar is not None and j < L - 1:
-                    src.append((pb(gbar[j], blk and j > 0), pb(s[j], blk), gm[j:j + 1], sm[j:j + 1]))
-                jobs.append((dst, wt is not None, src))
+                    src.append(WgradSource(pb(gbar[j], blk and j > 0), pb(s[j], blk), gm[j:j + 1], sm[j:j + 1]))
+                jobs.append(WgradJob(dst, wt is not None, src))
         wgrad_group(jobs)
         for j in range(L):
             if ctx.needs_input_grad[2 + NG + j] and nbar is not None and j == L - 1:

@@ -18,7 +18,7 @@ _vp = ctypes.c_void_p
 _CT = {"i": ctypes.c_int, "f": ctypes.c_float, "p": _vp, "q": _vp, "F": ctypes.POINTER(ctypes.c_float),
        "I": ctypes.POINTER(ctypes.c_int), "l": ctypes.c_longlong, "P": ctypes.POINTER(_vp),
        "A": ctypes.POINTER(ctypes.c_int), "L": ctypes.POINTER(ctypes.c_longlong), "x": _vp,
-       "W": ctypes.POINTER(ctypes.c_float)}
+       "W": ctypes.POINTER(ctypes.c_float), "u": ctypes.c_uint, "s": ctypes.c_char_p}
 
 # signature strings (without the trailing stream): i=int f=float l=long long p=device pointer
 # F=float[3] host  I=int[3] host  q=int32 device pointer (nullable)  x=device pointer of any dtype
@@ -149,6 +149,15 @@ for _p in ("voxel_hash_feature", "lanczos_voxel_hash_feature"):
     SIGS.update(_family(_p, "voxel_hash_feature", _HSH_TAIL))
     SIGS[f"{_p}_hash_index"] = "ippiiFFi"
 
+# stream-less entry points (sizes, counts, layouts, the group bracket): signature string (u=unsigned, s=char buffer, a trailing A=int
+# result), result type
+_i, _ll = ctypes.c_int, ctypes.c_longlong
+PROTOTYPES = {"hash_num_params": ("ifiii", _ll), "hash_grid_size": ("ifi", _i), "hash_table_size": ("ii", _i),
+              "mlp_packed_size": ("iii", _ll), "mlp_wgrad_workspace": ("iil", _ll), "mlp_chain_workspace": ("i", _ll),
+              "mlp_colsum_workspace": ("il", _ll), "mlp_wgrad_group_workspace": ("iPALAiAAiA", _ll),
+              "mlp_wgrad_group_launches": ("iLAi", _i), "mlp_chain_bias_partials": ("iliiAAiiiuiAA", _i),
+              "mlp_chain_kernel": ("iliiAAiiiisi", _i), "mlp_chain_group_end": ("pA", _i)}
+
 _lib = None
 _fns = {}
 
@@ -167,23 +176,9 @@ def load():
                 "`python -c 'import __graft_entry__ as g; g.build()'` (there is no CPU fallback).")
         _lib = ctypes.CDLL(SO_PATH)
         _lib.ndjir_version.restype = ctypes.c_char_p
-        _lib.ndjir_hash_num_params.restype = ctypes.c_longlong
-        _lib.ndjir_hash_num_params.argtypes = [ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        _lib.ndjir_hash_grid_size.argtypes = [ctypes.c_int, ctypes.c_float, ctypes.c_int]
-        _lib.ndjir_hash_table_size.argtypes = [ctypes.c_int, ctypes.c_int]
-        _lib.ndjir_mlp_packed_size.restype = ctypes.c_longlong
-        _lib.ndjir_mlp_packed_size.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        _lib.ndjir_mlp_wgrad_workspace.restype = ctypes.c_longlong
-        _lib.ndjir_mlp_wgrad_workspace.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_longlong]
-        _lib.ndjir_mlp_chain_workspace.restype = ctypes.c_longlong
-        _lib.ndjir_mlp_chain_workspace.argtypes = [ctypes.c_int]
-        _lib.ndjir_mlp_colsum_workspace.restype = ctypes.c_longlong
-        _lib.ndjir_mlp_colsum_workspace.argtypes = [ctypes.c_int, ctypes.c_longlong]
-        _lib.ndjir_mlp_wgrad_group_workspace.restype = ctypes.c_longlong
-        _lib.ndjir_mlp_wgrad_group_workspace.argtypes = [ctypes.c_int, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int),
-                                                         ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int),
-                                                         ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
-                                                         ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        for name, (sig, restype) in PROTOTYPES.items():
+            f = getattr(_lib, "ndjir_" + name)
+            f.argtypes, f.restype = [_CT[c] for c in sig], restype
     return _lib
 
 
@@ -212,11 +207,8 @@ def _i3(v):
     return (ctypes.c_int * 3)(int(v[0]), int(v[1]), int(v[2]))
 
 
-def call(name, *args):
-    """Launch entry point `ndjir_<name>` on the current torch HIP stream."""
-    f, sig = _fn(name)
-    if len(args) != len(sig):
-        raise TypeError(f"ndjir_{name}: expected {len(sig)} arguments, got {len(args)}")
+def _marshal(name, sig, args):
+    """`args` as the ctypes values of the signature string `sig`."""
     cargs = []
     for c, v in zip(sig, args):
         if c == "p":
@@ -266,10 +258,22 @@ def call(name, *args):
             cargs.append(float(v))
         else:
             cargs.append(int(v))
-    stream = torch.cuda.current_stream().cuda_stream
-    rc = f(*cargs, stream)
+    return cargs
+
+
+def call(name, *args):
+    """Launch entry point `ndjir_<name>` on the current torch HIP stream."""
+    f, sig = _fn(name)
+    if len(args) != len(sig):
+        raise TypeError(f"ndjir_{name}: expected {len(sig)} arguments, got {len(args)}")
+    rc = f(*_marshal(name, sig, args), torch.cuda.current_stream().cuda_stream)
     if rc != 0:
         raise NdjirHipError(f"ndjir_{name} failed with status {rc}")
+
+
+def query(name, *args):
+    """Value of the stream-less entry point `ndjir_<name>` (a size, a count), its arguments marshalled like `call`'s."""
+    return getattr(load(), "ndjir_" + name)(*_marshal(name, PROTOTYPES[name][0], args))
 
 
 def symbols():

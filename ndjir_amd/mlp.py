@@ -10,9 +10,12 @@ Backward: one fused chain launch for the data path (delta of every layer + bias 
 gradient); weight gradients H^T delta by the split-P MFMA kernel of csrc/wgrad.hip.
 """
 import contextlib
+import ctypes
 import dataclasses
+import functools
 import operator
 import os
+import typing
 import weakref
 
 import torch
@@ -63,7 +66,6 @@ def get_chain_pipeline():
 
 
 def _init_math():
-    import os
     env = os.environ.get("NDJIR_MLP_MATH")
     if env:
         set_math({"fp32": MATH_FP32, "bf16x6": MATH_BF16X6, "f16x3": MATH_F16X3}[env.lower()])
@@ -77,14 +79,10 @@ PROFILE = None
 def chain_kernel_symbol(mode, P, K0, Ks, Ns, has_output=True, skip_layer=-1, skip_split=0, with_bias_gradients=False):
     """The symbol (as rocprofv3 prints it) of the kernel a chain launch of this shape runs under the current arithmetic and
     tile setting: the library's own dispatch decision (ndjir_mlp_chain_kernel), nothing is launched."""
-    import ctypes
     L = len(Ks)
     buf = ctypes.create_string_buffer(64)
-    f = lib.load().ndjir_mlp_chain_kernel
-    f.argtypes = [ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
-                  ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
-    f.restype = ctypes.c_int
-    rc = f(int(mode), int(P), int(K0), L, (ctypes.c_int * L)(*[int(k) for k in Ks]), (ctypes.c_int * L)(*[int(n) for n in Ns]),
+    rc = lib.load().ndjir_mlp_chain_kernel(
+        int(mode), int(P), int(K0), L, (ctypes.c_int * L)(*[int(k) for k in Ks]), (ctypes.c_int * L)(*[int(n) for n in Ns]),
            1 if has_output else 0, int(skip_layer), int(skip_split), 1 if with_bias_gradients else 0, buf, 64)
     return buf.value.decode() if rc == 0 else f"ndjir chain (status {rc})"
 
@@ -200,7 +198,6 @@ def _defer_bias_reduction(call):
     (`set_grad_buffer`) does not reduce its per-workgroup partial rows itself (one small launch per chain, 13 per step): it
     leaves them in a private region and the step's one reduction launch sums them with the weight-gradient slabs.
     Returns a copy of the call with the DEFER flag and the region in place, or None when the launch does not qualify."""
-    import ctypes
     if _DEFERRED is None or int(call.mode) == 0 or not (int(call.accum_y) & ACCUM_BGRAD):
         return None
     if get_math() != MATH_F16X3:
@@ -217,13 +214,9 @@ def _defer_bias_reduction(call):
     lay = _BIAS_LAYOUT.get(key)
     if lay is None:
         blocks, row = ctypes.c_int(0), ctypes.c_int(0)
-        f = lib.load().ndjir_mlp_chain_bias_partials
-        f.argtypes = [ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
-                      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
-                      ctypes.POINTER(ctypes.c_int)]
-        f.restype = ctypes.c_int
-        rc = f(mode, P, K0, L, (ctypes.c_int * L)(*Ks), (ctypes.c_int * L)(*Ns), 1 if has_output else 0, skip, split, mask,
-               1 if in_bg is not None else 0, ctypes.byref(blocks), ctypes.byref(row))
+        rc = lib.load().ndjir_mlp_chain_bias_partials(
+            mode, P, K0, L, (ctypes.c_int * L)(*Ks), (ctypes.c_int * L)(*Ns), 1 if has_output else 0, skip, split, mask,
+            1 if in_bg is not None else 0, ctypes.byref(blocks), ctypes.byref(row))
         lay = _BIAS_LAYOUT[key] = (blocks.value, row.value) if rc == 0 else None
         if len(_BIAS_LAYOUT) > 4096:
             _BIAS_LAYOUT.clear()
@@ -237,10 +230,10 @@ def _defer_bias_reduction(call):
     off = 0
     for j, t in live:
         n = int(call.Ns[j])
-        _DEFERRED_BIAS.append((t, region[off:], n, blocks, row))
+        _DEFERRED_BIAS.append(BiasPartial(t, region[off:], n, blocks, row))
         off += n
     if in_bg is not None:
-        _DEFERRED_BIAS.append((in_bg, region[off:], K0, blocks, row))
+        _DEFERRED_BIAS.append(BiasPartial(in_bg, region[off:], K0, blocks, row))
         off += K0
     assert off <= row < off + 4, (off, row)          # (the launchers pad a partial row to a multiple of 4 floats)
     return dataclasses.replace(call, accum_y=int(call.accum_y) | DEFER_BGRAD, workspace=region)
@@ -283,7 +276,6 @@ def _group_class(call):
 
 
 def _flush_chain_group(calls):
-    import ctypes
     # runs of consecutive calls of one (mode, points, width class); the library decides which of them really share a launch
     i = 0
     while i < len(calls):
@@ -297,7 +289,6 @@ def _flush_chain_group(calls):
             _launch_chain_now(run[0])
             continue
         so = lib.load()
-        so.ndjir_mlp_chain_group_end.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
         n_launch = ctypes.c_int(0)
         stream = torch.cuda.current_stream().cuda_stream
         # profiling: one entry per group launch (the sum of its nets' algorithmic work; the input tile is counted once per
@@ -339,30 +330,21 @@ def _launch_chain_now(call):
     kind = call.kind
     if PROFILE is not None and not os.environ.get("NDJIR_MLP_TILE") and (int(call.P) + 63) // 64 < 256:
         kind += "_t32"            # small launch: the library picks 32-point tiles (a different kernel instantiation)
-    _launch_now(kind, call.flops, call.entry, call.args(), call.shape, call)
+    _launch(kind, call.flops, call.entry, *call.args(), shape=call.shape, nbytes=_chain_bytes(call) if PROFILE is not None else 0.0,
+            chain=call)
 
 
-def _launch(kind, flops, name, *args, shape=""):
-    _launch_now(kind, flops, name, args, shape)
-
-
-def _launch_now(kind, flops, name, args, shape, chain=None):
+def _launch(kind, flops, name, *args, shape="", nbytes=0.0, n_kernels=1, chain=None):
+    """`lib.call(name, *args)`.  For the profile alone: `nbytes` = the algorithmic HBM bytes of the launch, `n_kernels` = the kernel
+    launches the call issues, `chain` = the record of a chain launch (its kernel symbol is the library's dispatch decision)."""
     if PROFILE is None:
         lib.call(name, *args)
         return
     sym = _chain_symbol(chain) if chain is not None else _SYMBOLS.get(name, "ndjir::" + name)
-    e0 = torch.cuda.Event(enable_timing=True)
-    e1 = torch.cuda.Event(enable_timing=True)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     lib.call(name, *args)
     e1.record()
-    n_kernels = 1
-    if name == "mlp_wgrad_group":       # a grouped call is one kernel launch (+ one reduction) per argument block
-        import ctypes
-        n, m = int(args[0]), int(args[9])
-        n_kernels = max(1, int(lib.load().ndjir_mlp_wgrad_group_launches(
-            n, (ctypes.c_longlong * n)(*[int(p) for p in args[5]]), (ctypes.c_int * n)(*[int(o) for o in args[8]]), m)))
-    nbytes = _chain_bytes(chain) if chain is not None else _launch_bytes(name, args)
     PROFILE.append((kind, flops, e0, e1, shape, nbytes, sym, n_kernels))
 
 
@@ -378,20 +360,6 @@ def _chain_bytes(call):
     if call.Y is not None and int(call.has_output):
         n += P * int(call.Ns[int(call.L) - 1]) * (2 if int(call.accum_y) & ACCUM_Y else 1)
     return 4.0 * n
-
-
-def _launch_bytes(name, args):
-    """Algorithmic HBM bytes of a weight-gradient / column-sum launch (profiling only): both operands + the gradient."""
-    if name == "mlp_wgrad":
-        K, N, P = int(args[4]), int(args[5]), int(args[6])
-        return 4.0 * (P * (K + N) + K * N * (2 if int(args[8]) else 1))
-    if name == "mlp_colsum":
-        return 4.0 * int(args[2]) * int(args[3])
-    if name == "mlp_wgrad_group":
-        Ps, oid, Ks, Ns, acc = args[5], args[8], args[12], args[13], args[14]
-        n = sum(int(p) * (int(Ks[o]) + int(Ns[o])) for p, o in zip(Ps, oid))
-        return 4.0 * (n + sum(int(k) * int(m) * (2 if a else 1) for k, m, a in zip(Ks, Ns, acc)))
-    return 0.0
 
 
 _MATH_READY = False
@@ -624,13 +592,26 @@ class SplitTarget:
 _ROWS_TARGET = REG.rows_target      # first byte of a rows_except copy -> (shape, SplitTarget, owner view); valid while the buffers are registered
 
 
+# The pieces of a grouped weight gradient (`wgrad_group`; plain tuples in their order do as well): an operand pair with the slots of its
+# recorded maxima; an output (K, N) and the pairs whose A^T B are summed (with `accum`: added) into it; a deferred bias gradient
+WgradSource = typing.NamedTuple("WgradSource", [("A", object), ("B", object), ("amax_a", object), ("amax_b", object)])
+WgradJob = typing.NamedTuple("WgradJob", [("out", object), ("accum", bool), ("sources", list)])
+BiasPartial = typing.NamedTuple("BiasPartial", [("grad", object), ("partial", object), ("floats", int), ("rows", int), ("row_stride", int)])
+
+
+def _as_jobs(jobs):
+    """`jobs` as `WgradJob`s of `WgradSource`s with source lists of their own."""
+    return [WgradJob(out, accum, [WgradSource(*s) for s in sources]) for out, accum, sources in jobs]
+
+
 def wgrad_jobs(target, A, B, amax_a, amax_b):
     """Grouped-launch jobs that ADD A^T B to an accumulate-in-place `target` (`grad_target`): one job, or one per row block of
     a `SplitTarget` (a row block of dW = a column block of A; a bound of A's magnitude bounds every block)."""
     if isinstance(target, SplitTarget):
         a = target.a
-        return [(target.top, True, [(A[:, :a], B, amax_a, amax_b)]), (target.bottom, True, [(A[:, a:], B, amax_a, amax_b)])]
-    return [(target, True, [(A, B, amax_a, amax_b)])]
+        return [WgradJob(target.top, True, [WgradSource(A[:, :a], B, amax_a, amax_b)]),
+                WgradJob(target.bottom, True, [WgradSource(A[:, a:], B, amax_a, amax_b)])]
+    return [WgradJob(target, True, [WgradSource(A, B, amax_a, amax_b)])]
 
 
 def grad_target(t):
@@ -807,19 +788,19 @@ def chain_forward(x, weights, biases, beta=100.0, skip_layer=-1, skip_scale=1.0,
     return y, hidden, am
 
 
-_WORKSPACE = {}
+_WORKSPACE, _WORKSPACE_G = {}, {}      # scratch of the chain / per-layer launches; work table and slabs of the grouped weight gradient
 
 
-def _workspace(device, need):
-    """Scratch of a launch, one buffer per (device, stream): launches on different streams (the renderer issues its background
-    branch beside the foreground pass) must not share it."""
+def _workspace(device, need, pool=_WORKSPACE, floor=1 << 22):
+    """Scratch of a launch, one buffer of at least `floor` floats per (device, stream) in `pool`: launches on different streams
+    (the renderer issues its background branch beside the foreground pass) must not share it.  A buffer that would have to grow
+    under a graph capture stays as it is -- the capture has its address --: the launch gets a one-off the capture owns."""
     key = (device, torch.cuda.current_stream(device).cuda_stream) if device.type == "cuda" else (device, 0)
-    ws = _WORKSPACE.get(key)
+    ws = pool.get(key)
     if ws is None or ws.numel() < need:
         if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-            return torch.empty(need, device=device, dtype=torch.float32)      # owned by the graph being captured, not kept
-        ws = torch.empty(max(need, 1 << 22), device=device, dtype=torch.float32)
-        _WORKSPACE[key] = ws
+            return torch.empty(need, device=device, dtype=torch.float32)
+        ws = pool[key] = torch.empty(max(need, floor), device=device, dtype=torch.float32)
     return _held(ws)
 
 
@@ -838,16 +819,15 @@ def wgrad(A, B, out=None, accum=False, amax_a=None, amax_b=None):
         out = torch.empty((K, N), device=A.device, dtype=torch.float32)
         accum = False
     _launch("wgrad", 2.0 * P * K * N, "mlp_wgrad", _Strided(A), A.stride(0), _Strided(B), B.stride(0), K, N, P, out,
-            1 if accum else 0, ws, amax_a, amax_b, shape=f"{P}:{K}x{N}")
+            1 if accum else 0, ws, amax_a, amax_b, shape=f"{P}:{K}x{N}", nbytes=4.0 * (P * (K + N) + K * N * (2 if accum else 1)))
     return out
 
 
-_WORKSPACE_G = {}
 WGRAD_GROUP_ITEMS = int(os.environ.get("NDJIR_WGRAD_ITEMS", "0"))     # work items a grouped launch aims for (0 = the library's default)
 SELF_AMAX_MAX_ROWS = int(os.environ.get("NDJIR_WGRAD_SELF_AMAX_ROWS", "16384"))      # operand pairs without recorded maxima up to this many rows join a grouped launch
 _NO_GROUP = bool(os.environ.get("NDJIR_NO_WGRAD_GROUP"))            # A/B: every weight gradient through the per-layer kernel
-_DEFERRED = None       # None = off; else the list of pending (out, accum, sources) jobs of `deferred_wgrads`
-_DEFERRED_BIAS = []    # pending (bias gradient view, partial rows, floats, rows, row stride) of chain launches (`_defer_bias_reduction`)
+_DEFERRED = None       # None = off; else the list of pending `WgradJob`s of `deferred_wgrads`
+_DEFERRED_BIAS = []    # pending `BiasPartial`s of chain launches (`_defer_bias_reduction`)
 
 
 def _merge_same_destination(jobs):
@@ -856,81 +836,97 @@ def _merge_same_destination(jobs):
     (Destinations that merely OVERLAP -- a parameter and its columns 1.., the packed first-order pass -- are reduced by
     separate launches inside the library.)"""
     merged, index = [], {}
-    for out, accum, srcs in jobs:
-        key = (out.data_ptr(), tuple(out.shape), tuple(out.stride()))
-        i = index.get(key)
-        if i is not None and accum:
-            merged[i][2].extend(srcs)
-            continue
-        if i is None:
-            index[key] = len(merged)
-        merged.append([out, accum, list(srcs)])
-    return [tuple(j) for j in merged]
+    for job in _as_jobs(jobs):
+        key = (job.out.data_ptr(), tuple(job.out.shape), tuple(job.out.stride()))
+        if key in index and job.accum:
+            merged[index[key]].sources.extend(job.sources)
+        else:
+            index.setdefault(key, len(merged))      # (a destination overwritten again: later jobs still join its first job)
+            merged.append(job)
+    return merged
+
+
+_list = functools.partial(dataclasses.field, default_factory=list)
+
+
+@dataclasses.dataclass(slots=True)
+class WgradGroupCall:
+    """One grouped weight-gradient call.  The launch fields are the parameters of ndjir_mlp_wgrad_group (include/ndjir_hip.h) by
+    name and in order -- `args()` is the only place that turns them into a positional call --; `kind`, `flops` and `shape` are
+    what the profile records of the launch.  Entry i of the source lists belongs to output out_id[i]."""
+    n_src: int = 0
+    A: list = _list(); lda: list = _list(); B: list = _list(); ldb: list = _list()
+    P: list = _list(); amax_a: list = _list(); amax_b: list = _list(); out_id: list = _list()
+    n_out: int = 0
+    out: list = _list(); ldo: list = _list(); K: list = _list(); N: list = _list(); accum: list = _list()
+    workspace: object = None; target_items: int = 0; n_extra: int = 0
+    ex_out: list = _list(); ex_partial: list = _list(); ex_n: list = _list(); ex_S: list = _list()
+    ex_stride: list = _list(); ex_accum: list = _list(); layout: list = _list()
+    kind: str = "wgrad"; flops: float = 0.0; shape: str = ""
+
+    @classmethod
+    def build(cls, jobs, extras=()):
+        """The call that computes `jobs` (none: a reduce-only call) and sums the deferred bias gradients `extras` (`BiasPartial`s) in
+        its reduction; the workspace is left to the launcher.  Layout bits: 1 = A, 2 = B is point-blocked (`PB`)."""
+        jobs, ex = _as_jobs(jobs), [BiasPartial(*e) for e in extras]
+        c = cls(n_out=len(jobs), target_items=int(WGRAD_GROUP_ITEMS), n_extra=len(ex), ex_out=[_Strided(e.grad) for e in ex],
+                ex_partial=[_Strided(e.partial) for e in ex], ex_n=[e.floats for e in ex], ex_S=[e.rows for e in ex],
+                ex_stride=[e.row_stride for e in ex], ex_accum=[1] * len(ex))
+        for o, job in enumerate(jobs):
+            K, N = job.out.shape
+            assert job.out.stride(1) == 1 or N == 1
+            c.out.append(_Strided(job.out)); c.ldo.append(job.out.stride(0) if K > 1 else N)
+            c.K.append(K); c.N.append(N); c.accum.append(1 if job.accum else 0)
+            for s in job.sources:
+                P = s.A.shape[0]
+                assert s.A.shape[1] == K and s.B.shape == (P, N) and s.A.stride(1) == 1 and (s.B.stride(1) == 1 or N == 1)
+                c.A.append(_Strided(s.A)); c.lda.append(s.A.stride(0) if P > 1 else K)
+                c.B.append(_Strided(s.B)); c.ldb.append(s.B.stride(0) if P > 1 else N)
+                c.P.append(P); c.amax_a.append(s.amax_a); c.amax_b.append(s.amax_b); c.out_id.append(o)
+                c.layout.append((1 if isinstance(s.A, PB) else 0) | (2 if isinstance(s.B, PB) else 0))
+        c.n_src = len(c.A)
+        c.flops = 2.0 * sum(p * c.K[o] * c.N[o] for p, o in zip(c.P, c.out_id))
+        c.shape = f"group {c.n_out} out / {c.n_src} src {c.flops / 2e9:.1f} GMAC " + ",".join(
+            f"{p}:{c.K[o]}x{c.N[o]}" for p, o in list(zip(c.P, c.out_id))[:2])
+        return c
+
+    def args(self):
+        return _GROUP_ARGS(self)      # (the arguments of `lib.call("mlp_wgrad_group", ...)`)
+
+    def workspace_floats(self):
+        return int(lib.query("mlp_wgrad_group_workspace", self.n_src, self.A, self.lda, self.P, self.out_id, self.n_out, self.K, self.N,
+                             self.target_items, self.layout))
+
+    def n_launches(self):
+        """Kernel launches of the call: one of the grouped kernel (+ one reduction) per argument block."""
+        return max(1, int(lib.query("mlp_wgrad_group_launches", self.n_src, self.P, self.out_id, self.n_out)))
+
+    @property
+    def nbytes(self):
+        """Algorithmic HBM bytes (profiling only): both operands of every source + every gradient (twice when accumulated into)."""
+        n = sum(p * (self.K[o] + self.N[o]) for p, o in zip(self.P, self.out_id))
+        return 4.0 * (n + sum(k * m * (2 if a else 1) for k, m, a in zip(self.K, self.N, self.accum)))
+
+
+_GROUP_ARGS = operator.attrgetter(*[f.name for f in dataclasses.fields(WgradGroupCall)][:-3])
 
 
 def _wgrad_group_now(jobs, extras=()):
-    """jobs: [(out, accum, [(A, B, amax_a, amax_b), ...]), ...] -> ndjir_mlp_wgrad_group: one launch + one reduction launch
-    for all of them (a second reduction launch for destinations that overlap others').  extras: deferred bias gradients
-    (view, partial rows, floats, rows, row stride), summed by the same reduction."""
-    _wgrad_group_launch(_merge_same_destination(jobs), extras)
-
-
-def _wgrad_group_launch(jobs, extras=()):
-    import ctypes
-    if not jobs:
-        if not extras:
-            return
-        dev = extras[0][0].device
-        wkey = (dev, torch.cuda.current_stream(dev).cuda_stream)
-        ws = _WORKSPACE_G.get(wkey)
-        need = int(lib.load().ndjir_mlp_wgrad_group_workspace(0, None, None, None, None, 0, None, None, 0, None))
-        if ws is None or ws.numel() < need:
-            ws = _WORKSPACE_G[wkey] = torch.empty(max(need, 1 << 24), device=dev, dtype=torch.float32)
-        _held(ws)
-        ex = list(extras)
-        lib.call("mlp_wgrad_group", 0, None, [], None, [], [], None, None, [], 0, None, [], [], [], [], ws, 0, len(ex),
-                 [_Strided(e[0]) for e in ex], [_Strided(e[1]) for e in ex], [e[2] for e in ex], [e[3] for e in ex], [e[4] for e in ex],
-                 [1] * len(ex), [])
+    """ndjir_mlp_wgrad_group: one launch + one reduction launch for all the jobs (a second reduction launch for destinations that
+    overlap others'); the same reduction sums the deferred bias gradients `extras` (with no jobs it is all the call does)."""
+    call = WgradGroupCall.build(_merge_same_destination(jobs), extras)
+    if not call.n_src and not call.n_extra:
         return
-    A, lda, B, ldb, Ps, ama, amb, oid, outs, ldo, Ks, Ns, acc, lay = ([] for _ in range(14))
-    for o, (out, accum, srcs) in enumerate(jobs):
-        K, N = out.shape
-        assert out.stride(1) == 1 or N == 1
-        outs.append(_Strided(out))
-        ldo.append(out.stride(0) if K > 1 else N)
-        Ks.append(K); Ns.append(N); acc.append(1 if accum else 0)
-        for a, b, ma, mb in srcs:
-            assert a.shape[1] == K and b.shape[1] == N and a.shape[0] == b.shape[0] and a.stride(1) == 1 and (b.stride(1) == 1 or N == 1)
-            A.append(_Strided(a)); lda.append(a.stride(0) if a.shape[0] > 1 else K)
-            B.append(_Strided(b)); ldb.append(b.stride(0) if b.shape[0] > 1 else N)
-            Ps.append(a.shape[0]); ama.append(ma); amb.append(mb); oid.append(o)
-            lay.append((1 if isinstance(a, PB) else 0) | (2 if isinstance(b, PB) else 0))
-    dev = jobs[0][0].device
-    n, m = len(A), len(jobs)
     if os.environ.get("NDJIR_WGRAD_DEBUG"):       # operand bytes of the launch by layout (0 row-major, 1 A / 2 B / 3 both blocked)
         by = {}
-        for i in range(n):
-            by[lay[i]] = by.get(lay[i], 0) + 4e-6 * Ps[i] * (Ks[oid[i]] + Ns[oid[i]])
-        print("wgrad group:", n, "sources;", {k: round(v, 1) for k, v in sorted(by.items())}, "MB by layout;",
-              sorted(__import__("collections").Counter((Ps[i], Ks[oid[i]], Ns[oid[i]], lay[i]) for i in range(n)).items()), flush=True)
-    vp = ctypes.c_void_p
-    need = int(lib.load().ndjir_mlp_wgrad_group_workspace(
-        n, (vp * n)(*[t.data_ptr() for t in A]), (ctypes.c_int * n)(*lda), (ctypes.c_longlong * n)(*Ps), (ctypes.c_int * n)(*oid),
-        m, (ctypes.c_int * m)(*Ks), (ctypes.c_int * m)(*Ns), int(WGRAD_GROUP_ITEMS), (ctypes.c_int * n)(*lay)))
-    wkey = (dev, torch.cuda.current_stream(dev).cuda_stream)      # (the work table and the slabs: one set per stream, like `_workspace`)
-    ws = _WORKSPACE_G.get(wkey)
-    if ws is None or ws.numel() < need:
-        if torch.cuda.is_current_stream_capturing():
-            ws = torch.empty(need, device=dev, dtype=torch.float32)      # owned by the graph being captured, not kept
-        else:
-            ws = _WORKSPACE_G[wkey] = torch.empty(max(need, 1 << 24), device=dev, dtype=torch.float32)
-    _held(ws)
-    flops = 2.0 * sum(p * Ks[o] * Ns[o] for p, o in zip(Ps, oid))
-    ex = list(extras)
-    _launch("wgrad", flops, "mlp_wgrad_group", n, A, lda, B, ldb, Ps, ama, amb, oid, m, outs, ldo, Ks, Ns, acc, ws, int(WGRAD_GROUP_ITEMS),
-            len(ex), [_Strided(e[0]) for e in ex], [_Strided(e[1]) for e in ex], [e[2] for e in ex], [e[3] for e in ex],
-            [e[4] for e in ex], [1] * len(ex), lay,
-            shape=f"group {m} out / {n} src {flops / 2e9:.1f} GMAC " + ",".join(f"{p}:{Ks[o]}x{Ns[o]}" for p, o in list(zip(Ps, oid))[:2]))
+        for p, o, lay in zip(call.P, call.out_id, call.layout):
+            by[lay] = by.get(lay, 0) + 4e-6 * p * (call.K[o] + call.N[o])
+        print("wgrad group:", call.n_src, "sources;", {k: round(v, 1) for k, v in sorted(by.items())}, "MB by layout;",
+              sorted(__import__("collections").Counter((p, call.K[o], call.N[o], lay) for p, o, lay in zip(call.P, call.out_id, call.layout)).items()), flush=True)
+    dev = (call.out or call.ex_out)[0].t.device
+    call.workspace = _workspace(dev, call.workspace_floats(), _WORKSPACE_G, 1 << 24)
+    _launch(call.kind, call.flops, "mlp_wgrad_group", *call.args(), shape=call.shape, nbytes=call.nbytes if PROFILE is not None else 0.0,
+            n_kernels=call.n_launches() if PROFILE is not None else 1)
 
 
 def wgrad_group(jobs):
@@ -941,30 +937,30 @@ def wgrad_group(jobs):
     and launched together when the block ends.  An operand without a recorded maximum makes the kernel's work items find
     their own (an extra pass over their rows: fine for the per-ray layers' few hundred rows; from SELF_AMAX_MAX_ROWS rows on
     such a pair takes the per-layer kernel with its streaming pre-pass).  Any arithmetic but f16x3: the per-layer kernel."""
-    jobs = [(o, a, [s for s in srcs if s[0].shape[0] > 0]) for o, a, srcs in jobs]
     grouped = []
-    for out, accum, srcs in jobs:
+    for job in _as_jobs(jobs):
+        out, srcs = job.out, [s for s in job.sources if s.A.shape[0] > 0]
         narrow = out.shape[1] <= 8
         ok = not _NO_GROUP and get_math() == MATH_F16X3 and out.is_cuda and srcs and all(
-            (narrow or (ma is not None and mb is not None) or a.shape[0] <= SELF_AMAX_MAX_ROWS) for a, _, ma, mb in srcs)
+            (narrow or (s.amax_a is not None and s.amax_b is not None) or s.A.shape[0] <= SELF_AMAX_MAX_ROWS) for s in srcs)
         if ok:
-            grouped.append((out, accum, srcs))
+            grouped.append(job._replace(sources=srcs))
             continue
-        assert not any(isinstance(a, PB) or isinstance(b, PB) for a, b, _, _ in srcs), "point-blocked operands need the grouped kernel"
-        first = not accum
+        assert not any(isinstance(s.A, PB) or isinstance(s.B, PB) for s in srcs), "point-blocked operands need the grouped kernel"
+        first = not job.accum
         if not srcs and first:
             out.zero_()
-        for a, b, ma, mb in srcs:
+        for s in srcs:
             if out.is_contiguous():
-                wgrad(a, b, out=out, accum=not first, amax_a=ma, amax_b=mb)
+                wgrad(s.A, s.B, out=out, accum=not first, amax_a=s.amax_a, amax_b=s.amax_b)
             elif first:
-                out.copy_(wgrad(a, b, amax_a=ma, amax_b=mb))
+                out.copy_(wgrad(s.A, s.B, amax_a=s.amax_a, amax_b=s.amax_b))
             else:
-                out.add_(wgrad(a, b, amax_a=ma, amax_b=mb))
+                out.add_(wgrad(s.A, s.B, amax_a=s.amax_a, amax_b=s.amax_b))
             first = False
     if not grouped:
         return
-    if _DEFERRED is not None and all(a for _, a, _ in grouped):
+    if _DEFERRED is not None and all(job.accum for job in grouped):
         _DEFERRED.extend(grouped)
         return
     _wgrad_group_now(grouped)
@@ -987,8 +983,7 @@ def deferred_wgrads():
         jobs, extras = _DEFERRED, list(_DEFERRED_BIAS)
         _DEFERRED = None
         del _DEFERRED_BIAS[:]
-        if jobs or extras:
-            _wgrad_group_now(jobs, extras)
+        _wgrad_group_now(jobs, extras)
     finally:
         _DEFERRED = None
         del _DEFERRED_BIAS[:]
@@ -1003,7 +998,7 @@ def colsum(X, out=None, accum=False):
         accum = False
     ws = _workspace(X.device, lib.load().ndjir_mlp_colsum_workspace(N, P))
     _launch("colsum", float(P) * N, "mlp_colsum", _Strided(X), X.stride(0) if P > 1 else N, N, P, out, 1 if accum else 0, ws,
-            shape=f"{P}:{N}")
+            shape=f"{P}:{N}", nbytes=4.0 * N * P)
     return out
 
 
@@ -1213,22 +1208,22 @@ class FusedMLP(Function):
             jobs = []           # every weight gradient of the net: one grouped launch (or queued: `deferred_wgrads`)
             for j in range(L):
                 if ctx.needs_input_grad[7 + j]:
-                    src = [(pb(A[j], blk and j > 0), pb(deltas[j], blk and j < L - 1), _slot(am, j), _slot(dm, j) if have_dm else None)]
+                    src = WgradSource(pb(A[j], blk and j > 0), pb(deltas[j], blk and j < L - 1), _slot(am, j), _slot(dm, j) if have_dm else None)
                     if tail and j == L - 1:
                         # the gradient of W[:, 1:] added to / placed in the parameter's columns 1.. (row stride = its width)
                         wt = grad_target(saved[2 * L - 1])
                         if wt is not None:
-                            jobs.append((wt[:, 1:], True, src))
+                            jobs.append(WgradJob(wt[:, 1:], True, [src]))
                         else:
                             gW[j] = torch.zeros_like(saved[2 * L - 1])
-                            jobs.append((gW[j][:, 1:], False, src))
+                            jobs.append(WgradJob(gW[j][:, 1:], False, [src]))
                     else:
                         wt = grad_target(W[j])
                         if wt is not None:
-                            jobs += wgrad_jobs(wt, *src[0])
+                            jobs += wgrad_jobs(wt, *src)
                         else:
                             gW[j] = torch.empty(tuple(W[j].shape), device=x2.device, dtype=torch.float32)
-                            jobs.append((gW[j], False, src))
+                            jobs.append(WgradJob(gW[j], False, [src]))
             wgrad_group(jobs)
             for j in range(L):
                 if ctx.needs_input_grad[7 + L + j]:
@@ -1398,13 +1393,13 @@ class MultiMLP(Function):
             jobs = []
             for j in range(L):
                 if nW[j]:
-                    src = [(pb(A[j], blk and j > 0), pb(deltas[j], blk and j < L - 1), _slot(am, j), _slot(dm, j))]
+                    src = WgradSource(pb(A[j], blk and j > 0), pb(deltas[j], blk and j < L - 1), _slot(am, j), _slot(dm, j))
                     wt = grad_target(W[j])
                     if wt is not None:
-                        jobs += wgrad_jobs(wt, *src[0])
+                        jobs += wgrad_jobs(wt, *src)
                     else:
                         out[wo - 4 + j] = torch.empty(tuple(W[j].shape), device=dev, dtype=torch.float32)
-                        jobs.append((out[wo - 4 + j], False, src))
+                        jobs.append(WgradJob(out[wo - 4 + j], False, [src]))
             wgrad_group(jobs)
             for j in range(L):
                 if nb[j]:

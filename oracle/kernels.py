@@ -8,6 +8,7 @@ Every function mirrors one pybind11 entry point of the reference's native module
 order; arrays are C-contiguous float32 numpy arrays updated in place.
 """
 import ctypes
+import fcntl
 import os
 import subprocess
 
@@ -21,9 +22,17 @@ MODE_LINEAR, MODE_COSINE = 0, 1
 
 def build(force=False):
     src = os.path.join(_HERE, "csrc", "ndjir_oracle.c")
-    if force or not os.path.exists(_SO) or (
-            os.path.exists(src) and os.path.getmtime(src) > os.path.getmtime(_SO)):
-        subprocess.check_call(["make", "-C", _HERE, "-s"] + (["-B"] if force else []))
+
+    def stale():
+        return not os.path.exists(_SO) or (os.path.exists(src) and os.path.getmtime(src) > os.path.getmtime(_SO))
+    if force or stale():
+        # one builder at a time: the ranks of a multi-process test reach this together, and a second `make` rewriting the
+        # library while the first rank loads it ends in "file too short" (tests/test_distributed_cpu.py)
+        os.makedirs(os.path.dirname(_SO), exist_ok=True)
+        with open(_SO + ".lock", "w") as lock:
+            fcntl.flock(lock, fcntl.LOCK_EX)
+            if force or stale():
+                subprocess.check_call(["make", "-C", _HERE, "-s"] + (["-B"] if force else []))
     return _SO
 
 

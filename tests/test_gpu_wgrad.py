@@ -437,6 +437,38 @@ def test_more_sources_than_one_table_holds(gpu, n_out, per_out, monkeypatch):
     _judge_specs(f"{n_out} outputs x {per_out} operand pairs: two tables", specs, _run_specs(specs, gpu))
 
 
+def test_reduce_only_call_sums_deferred_bias_partials(gpu, monkeypatch):
+    """A grouped call without jobs (what `deferred_wgrads` ends in when only bias gradients were deferred): two bias destinations
+    of 8 and 3 floats, three partial rows each in one region of row stride 12, ADDED to non-zero destinations -- against the fp64
+    sum, to the tolerance of test_gpu_mlp.py::test_colsum_kernel.  Eagerly, then under a graph capture."""
+    from ndjir_amd import mlp
+    rng = np.random.RandomState(81)
+    region = rng.randn(3, 12).astype(np.float32)
+    prev = [rng.randn(8).astype(np.float32), rng.randn(3).astype(np.float32)]
+    ref = [prev[0].astype(np.float64) + region[:, :8].astype(np.float64).sum(0), prev[1].astype(np.float64) + region[:, 8:11].astype(np.float64).sum(0)]
+    part, dst = torch.from_numpy(region).to(gpu).view(-1), [torch.from_numpy(p.copy()).to(gpu) for p in prev]
+    mlp._wgrad_group_now([], [mlp.BiasPartial(dst[0], part, 8, 3, 12), mlp.BiasPartial(dst[1], part[8:], 3, 3, 12)])
+    torch.cuda.synchronize()
+    for got, want in zip(dst, ref):
+        err = float(np.abs(got.cpu().numpy().astype(np.float64) - want).max()) / max(float(np.abs(want).max()), 1.0)
+        print(f"\nreduce-only call, {want.size} floats: error / scale {err:.2e}")
+        assert err < 2e-5
+    assert torch.equal(part.cpu(), torch.from_numpy(region).view(-1))          # (the partial rows are only read)
+    # ... and captured into a graph on a stream that has no workspace yet: the capture gets a one-off of its own and nothing is cached
+    # for later launches to share (`hold_buffers`); every replay adds the three rows once more
+    monkeypatch.setattr(mlp, "_WORKSPACE_G", {})
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        mlp._wgrad_group_now([], [mlp.BiasPartial(dst[0], part, 8, 3, 12), mlp.BiasPartial(dst[1], part[8:], 3, 3, 12)])
+    assert mlp._WORKSPACE_G == {}
+    graph.replay()
+    graph.replay()
+    torch.cuda.synchronize()
+    for got, want, p in zip(dst, ref, prev):
+        want = 3.0 * want - 2.0 * p.astype(np.float64)
+        assert float(np.abs(got.cpu().numpy().astype(np.float64) - want).max()) / max(float(np.abs(want).max()), 1.0) < 2e-5
+
+
 def test_one_output_with_more_pairs_than_a_table_is_refused(gpu):
     """193 operand pairs of ONE output fit no table (4 x 193 segments > 768): the library's error, before any launch -- the
     destination keeps its bits."""
