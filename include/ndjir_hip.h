@@ -40,6 +40,7 @@ extern "C" {
 #define NDJIR_ERR_LAUNCH 1
 #define NDJIR_ERR_UNSUPPORTED 2
 #define NDJIR_ERR_ARG 3
+#define NDJIR_ERR_CAPACITY 4
 
 const char* ndjir_version(void);
 int ndjir_zero(float* p, long long n, hipStream_t stream);
@@ -746,6 +747,49 @@ int ndjir_envmap_directions(int H, float* dirs, hipStream_t stream);
  * mirrored left-right (there :255 reverses the columns, sic). */
 int ndjir_envmap_quantize(int H, int W, int C, const float* intensity, const float* min_max, int sigmoid_mode,
                           unsigned char* image, hipStream_t stream);
+
+/* ---- mesh trimming and splitting (trim.hip; python/extract_by_mc.py:77-128) --------------------------------------------
+ * All results are integers and equal the reference's exactly.  uint8 buffers hold 0 / 1.
+ *
+ * ndjir_mask_dilate: the per-view mask of `clean_points_by_mask` (:89-96).  masks (M, H, W) fp32, a pixel is set when its
+ * value is >= 0.5; r in [0, 127]; half_widths: HOST table of 2r + 1 ints in [0, 127], the structuring element is
+ * {(dy, dx): |dx| <= half_widths[dy + r]}.  out (M, H + 2, W + 2) uint8: the one-pixel frame is 1, interior (y, x) is 1
+ * iff a set pixel lies under the element anchored at (y, x); pixels outside the image contribute nothing (cv2's default
+ * border for dilate).  row_dist: workspace of M * H * W bytes (per pixel the distance to the nearest set pixel of its row).
+ * M <= 65535, H <= 65535, H * W < 2^31. */
+int ndjir_mask_dilate(int M, int H, int W, const float* masks, int r, const int* half_widths, unsigned char* row_dist,
+                      unsigned char* out, hipStream_t stream);
+/* `clean_points_by_mask`'s projection and lookup (:85-87, :98): points (N, 3) fp32, widened exactly to fp64; cams (M, 21)
+ * fp64 on the device, row m = [K (9, row-major) | R (9) | t (3)] of view m (world -> camera); padded_masks (M, H + 2, W + 2)
+ * from ndjir_mask_dilate.  Per view, in fp64 without contraction and in numpy's order: q = R p + t, u = K q, u / u_z,
+ * ix = rint(u_x) + 1 clipped to [0, W + 1], iy likewise to [0, H + 1]; a non-finite or out-of-range coordinate lands on
+ * the frame (inside), as numpy's int32 cast followed by the clip does.  keep (N,) uint8 = AND over the views.  M == 0
+ * keeps everything. */
+int ndjir_points_in_masks(long long N, const float* points, int M, int H, int W, const unsigned char* padded_masks,
+                          const double* cams, unsigned char* keep, hipStream_t stream);
+/* Stable compaction of flags (:111-113): keep (N,) uint8 -> new_index (N,) int32 = number of set flags before i where
+ * keep[i], -1 elsewhere; count (2 ints on the device): count[0] = number of set flags, count[1] = 0.  Optionally moves rows:
+ * rows (N, row_width) fp32 -> out_rows[new_index[i]] = rows[i] (both null to skip).  workspace: ceil(N / 1024) ints.
+ * Input order is kept (wave ballots, block offsets from a one-block scan of the block totals; no per-element atomics). */
+int ndjir_compact_flags(long long N, const unsigned char* keep, int* new_index, int* count, int* workspace, const float* rows,
+                        int row_width, float* out_rows, hipStream_t stream);
+/* Faces whose three vertices survive (:115-119): faces (F, 3) int32 with vertex indices in [0, N), new_index (N,) from
+ * ndjir_compact_flags, face_keep (F,) uint8 or null (a further condition on the face itself).  out_faces (capacity F, 3):
+ * the surviving faces in input order with their indices remapped; count (2 ints on the device): count[0] = their number,
+ * count[1] != 0 if a face named a vertex outside [0, N) (such a face is dropped).  workspace: ceil(F / 1024) ints. */
+int ndjir_trim_faces(long long F, const int* faces, const unsigned char* face_keep, long long N, const int* new_index,
+                     int* out_faces, int* count, int* workspace, hipStream_t stream);
+/* Connected components of faces joined through shared undirected edges (what trimesh's split(only_watertight=False) does
+ * through face_adjacency, :124; a shared vertex alone does not connect, an edge of three or more faces connects all of
+ * them, an edge from a vertex to itself is ignored).  faces (F, 3) int32, indices in [0, N).  labels (F,) int32:
+ * labels[f] = the smallest face index of f's component -- canonical, independent of scheduling.  Workspace: an
+ * open-addressing table of `slots` entries, a power of two, keys (slots,) 64-bit and owner (slots,) int32 (no
+ * initialisation needed); it must hold every distinct edge (at most 3F; 2 * 3F keeps probe chains short).  status: one int
+ * on the device.  Unlike the other entry points this one WAITS for the stream, to return the error code: NDJIR_ERR_CAPACITY
+ * when the table is full, NDJIR_ERR_ARG for a vertex index out of range or an exhausted retry bound (labels are then
+ * unspecified).  Every probe, hook and walk is bounded; no input spins. */
+int ndjir_face_components(long long F, const int* faces, long long N, long long slots, unsigned long long* keys, int* owner,
+                          int* labels, int* status, hipStream_t stream);
 
 #ifdef __cplusplus
 }

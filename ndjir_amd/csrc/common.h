@@ -6,6 +6,7 @@
 #define NDJIR_ERR_LAUNCH 1        // hipGetLastError() != hipSuccess after a launch
 #define NDJIR_ERR_UNSUPPORTED 2   // argument combination has no kernel
 #define NDJIR_ERR_ARG 3           // invalid argument (null pointer, bad size)
+#define NDJIR_ERR_CAPACITY 4      // a caller-sized table is too small for the input (ndjir_face_components)
 
 namespace ndjir {
 

@@ -16,9 +16,14 @@ extract_by_mc.py:144-261): the caller brings the mesh (vertices and faces, e.g. 
 `bake_vertex_attributes` evaluates the geometric net with its gradient once per vertex and the four material nets once on
 the packed input, and one head launch (csrc/bake.hip) turns their raw outputs into the six textures -- the reference runs
 the geometric net and `nn.grad` six times per vertex, once per texture.  `extract_environment_map` builds the direction
-lattice, evaluates the environment light net and quantises on the device.  Out of scope: marching cubes, mask trimming
-and mesh splitting (`clean_points_by_mask`, `create_trimmed_meshes`, `create_largest_meshes`, :77-141: cv2 morphology and
-connected components), and sharding the vertices over ranks.
+lattice, evaluates the environment light net and quantises on the device.
+
+Trimming (`clean_points_by_mask`, `create_trimmed_meshes`, :77-128): `create_trimmed_meshes` dilates the scene's masks,
+tests every vertex against every view, drops what falls outside and splits the rest into components, all on the device
+(ndjir_amd/trim.py, csrc/trim.hip) and equal to the reference's integers; `extract(..., source=...)` writes the `trimmed`
+meshes.  Out of scope: marching cubes; `create_largest_meshes` (:131-141, never called by `extract`); trimesh's merging of
+bit-identical vertices and its exclusion of edges shared by more than two faces; fp64 vertices; sharding the vertices over
+ranks.
 """
 import os
 
@@ -227,8 +232,31 @@ def save_attributed_mesh(dirname, fname, verts, faces, conf, train=False, type="
     return fpath
 
 
-def extract(dirname, fname, conf, verts, faces, train=False):
-    """`extract` (extract_by_mc.py:263-288) without its marching-cubes and trimming steps: the environment map, then the
-    raw mesh `verts`, `faces` with its six textures.  Returns the last mesh path."""
+def create_trimmed_meshes(verts, faces, source, conf, pixel_margin=50, max_meshes=5):
+    """`create_trimmed_meshes` (extract_by_mc.py:105-128) for the scene of `source` (an `IDRRaySource`: masks, intrinsics and
+    poses on the device): the vertices that project into every view's mask, dilated by `pixel_margin` pixels, the faces they
+    keep, split into components.  Returns [(verts_k, faces_k), ...] on the device, largest first (`trim.split_components`),
+    at most `max_meshes`; [] when nothing survives.  The image size is the masks' (the reference hard-codes 1600 x 1200)."""
+    from . import trim
+    masks = source.masks.view(source._size, source._H, source._W)
+    padded = trim.dilate_masks(masks, pixel_margin)
+    cams = trim.camera_table(source.intrinsics, source.poses)
+    keep = trim.points_inside_masks(verts, padded, cams)
+    new_verts, new_faces = trim.trim_mesh(verts, faces, keep)
+    if new_faces.shape[0] == 0:
+        return []
+    return trim.split_components(new_verts, new_faces, max_meshes)[0]
+
+
+def extract(dirname, fname, conf, verts, faces, train=False, source=None):
+    """`extract` (extract_by_mc.py:263-288) without its marching-cubes step: the environment map, then the raw mesh `verts`,
+    `faces` with its six textures; with a `source` (an `IDRRaySource`) and not `train`, also the trimmed meshes
+    `..._trimmed_..._mesh{k:02d}.obj` for k = min(n, 5) - 1 ... 0 (:281-286; whether the scene is a DTU scan, the reference's
+    `check_dtu_data`, is the caller's decision).  Returns the last mesh path."""
     extract_environment_map(dirname, conf)
-    return save_attributed_mesh(dirname, fname, verts, faces, conf, train, "raw", 0)
+    fpath = save_attributed_mesh(dirname, fname, verts, faces, conf, train, "raw", 0)
+    if source is not None and not train:
+        meshes = create_trimmed_meshes(verts, faces, source, conf)
+        for k in range(min(len(meshes), 5) - 1, -1, -1):
+            fpath = save_attributed_mesh(dirname, fname, meshes[k][0], meshes[k][1], conf, train, "trimmed", k)
+    return fpath

@@ -117,6 +117,16 @@ SIGS = {
     "bake_scale": "lppq",
     "envmap_directions": "ip",
     "envmap_quantize": "iiippix",
+    # M H W masks r half_widths[2r+1] row_dist out
+    "mask_dilate": "iiipiAxx",
+    # N points M H W padded_masks cams keep
+    "points_in_masks": "lpiiixxx",
+    # N keep new_index count[2] workspace rows row_width out_rows
+    "compact_flags": "lxqqqpip",
+    # F faces face_keep N new_index out_faces count[2] workspace
+    "trim_faces": "lqxlqqqq",
+    # F faces N slots keys owner labels status
+    "face_components": "lqllxqqq",
     "solver_adam_begin": "xffqq",
     # n w g m v alpha_t beta1 beta2 eps decay zero_grad state
     "solver_adam": "lppppfffffix",
