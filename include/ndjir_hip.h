@@ -791,6 +791,43 @@ int ndjir_trim_faces(long long F, const int* faces, const unsigned char* face_ke
 int ndjir_face_components(long long F, const int* faces, long long N, long long slots, unsigned long long* keys, int* owner,
                           int* labels, int* status, hipStream_t stream);
 
+/* ---- marching cubes (mc.hip; replaces skimage.measure.marching_cubes of python/extract_by_mc.py:36-43) -----------------
+ * vol (Gx, Gy, Gz) fp32, vol[i, j, k] at linear index (i * Gy + j) * Gz + k; each G in [2, 2^15], Gx * Gy * Gz < 2^31.
+ * A point is inside iff vol < level (equality and -0.0 at level 0 are outside).  One vertex per lattice edge whose endpoints
+ * differ, ordered by (linear index of the edge's lower point, axis x < y < z).  Faces by the rule in mc.hip's header (runs
+ * of inside corners on each cell face, walked counter-clockwise from outside, give directed segments that link into loops),
+ * ordered by (linear index of the cell's origin point, table order).  No atomics: order is fully determined.
+ *
+ * Numbering inside a cell: corner bit c = dx + 2 dy + 4 dz (bit c of the case byte is set iff that corner is inside);
+ * cube edge e = 4 * axis + r, r = the rank of the edge's lower corner among the four corners with d_axis == 0 in ascending
+ * corner number (x edges: lower corners 0, 2, 4, 6; y edges: 0, 1, 4, 5; z edges: 0, 1, 2, 3).
+ *
+ * ndjir_mc_case_table: HOST-only, no device work.  Fills host_table (256 x 16 bytes) by running the rule in host code:
+ * row[0] = number of triangles of the case (<= 5), row[1 + 3 t .. 3 + 3 t] = the cube edges of triangle t in the "descent"
+ * winding (counter-clockwise seen from the higher-value side: normals toward increasing values); unused bytes are 0.  The
+ * caller uploads the table once per device and passes the device pointer as `table` below. */
+int ndjir_mc_case_table(unsigned char* host_table);
+/* Count pass and scan.  code (N,) uint16, N = Gx Gy Gz: per point, low byte = the case byte of the cell whose origin the point
+ * is (0 for a point on the volume's upper faces), bits 8-10 = which of its own +x / +y / +z edges cross.  block_sums: 2 * nb
+ * ints, nb = ceil(N / 1024); on return block_sums[b] = number of vertices owned by the points before block b's 1024 points,
+ * block_sums[nb + b] = number of triangles of the cells before them.  counts (4 ints on the device): [0] = vertices,
+ * [1] = triangles (each capped at 2^31 - 1), [2] / [3] != 0 if the vertex / triangle total exceeds 2^31 - 1 (the offsets are
+ * then meaningless and ndjir_mc_emit must not be called).  Volume traffic: 4 B read + 2 B written per point. */
+int ndjir_mc_count(int Gx, int Gy, int Gz, const float* vol, float level, const unsigned char* table, unsigned short* code,
+                   int* block_sums, int* counts, hipStream_t stream);
+/* Emit pass, after the caller read counts and allocated verts (V, 3) fp32 and faces (F, 3) int32 with V = counts[0],
+ * F = counts[1].  code and block_offsets as ndjir_mc_count left them.  Vertex on the edge from point p along axis a:
+ * t = (level - v0) / (v1 - v0) in fp32 (correctly rounded), lattice position float(index) + t on axis a, float(index) on
+ * the others; world position pos * scale[b] + mins[b] per axis b as an fp32 multiply followed by an fp32 add, never fused
+ * (scale = {1, 1, 1}, mins = {0, 0, 0} leaves lattice coordinates).  scale, mins: HOST arrays of 3 floats.  vertex_base (N,)
+ * int32 workspace (no initialisation needed): the number of vertices owned by the points before p, written only where p
+ * owns a vertex.  table must be 4-byte aligned.  ascent != 0 swaps the last two indices of every face.  Stores are guarded by
+ * V and F.  Traffic: 2 B read per point for the vertices and 2 B for the faces, plus the rows and lookups of the active
+ * cells. */
+int ndjir_mc_emit(int Gx, int Gy, int Gz, const float* vol, float level, const unsigned char* table, const unsigned short* code,
+                  const int* block_offsets, const float* scale, const float* mins, int ascent, int* vertex_base, float* verts,
+                  long long V, int* faces, long long F, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

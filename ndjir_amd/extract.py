@@ -5,14 +5,19 @@ Reference: `compute_pts_vol` (python/extract_by_mc.py:46-74): G^3 points of a re
 copied to the device, evaluated layer by layer, and its 257-column output copied back.  Here the lattice
 points are formed on the device chunk by chunk, the geometric net runs as the fused sdf-only MFMA chain
 (grid gather + 8 layers in one launch sequence, only column 0 of the last layer is computed) and the volume
-stays on the device until the caller asks for it.  Marching cubes itself is out of scope (skimage on the CPU
-in the reference, `extract_by_mc.py:31-43`).
+stays on the device until the caller asks for it.
+
+Marching cubes (`create_mesh_from_volume`, :36-43; skimage on the CPU in the reference) runs on the device too
+(ndjir_amd/mc.py, csrc/mc.hip): a rule-defined isosurface with a generated case table, fp32 vertices, output order fixed by
+prefix sums.  Its vertices are those of any marching cubes; its connectivity can differ from skimage's Lewiner variant in
+ambiguous cells, and which winding skimage calls "descent" is UNPINNED (see mc.py).  `extract_scene` is the reference's
+whole `extract` (:263-288): volume, mesh, textures, files.
 
 The lattice shards over x-slabs: `slab_range(G, rank, world)`; each rank evaluates its slabs independently
 (no collective on the data path), `gather_volume` concatenates them.
 
 Export half (`compute_vertex_colors`, `create_rgb_color`, `save_attributed_mesh`, `extract_environment_map`, `extract`;
-extract_by_mc.py:144-261): the caller brings the mesh (vertices and faces, e.g. from marching cubes over `compute_vol`).
+extract_by_mc.py:144-261): these take a mesh (vertices and faces), from `create_mesh_from_volume` or the caller's own.
 `bake_vertex_attributes` evaluates the geometric net with its gradient once per vertex and the four material nets once on
 the packed input, and one head launch (csrc/bake.hip) turns their raw outputs into the six textures -- the reference runs
 the geometric net and `nn.grad` six times per vertex, once per texture.  `extract_environment_map` builds the direction
@@ -21,7 +26,7 @@ lattice, evaluates the environment light net and quantises on the device.
 Trimming (`clean_points_by_mask`, `create_trimmed_meshes`, :77-128): `create_trimmed_meshes` dilates the scene's masks,
 tests every vertex against every view, drops what falls outside and splits the rest into components, all on the device
 (ndjir_amd/trim.py, csrc/trim.hip) and equal to the reference's integers; `extract(..., source=...)` writes the `trimmed`
-meshes.  Out of scope: marching cubes; `create_largest_meshes` (:131-141, never called by `extract`); trimesh's merging of
+meshes.  Out of scope: `create_largest_meshes` (:131-141, never called by `extract`); trimesh's merging of
 bit-identical vertices and its exclusion of edges shared by more than two faces; fp64 vertices; sharding the vertices over
 ranks.
 """
@@ -95,6 +100,17 @@ def compute_pts_vol(mins, maxs, grid_size, conf, **kw):
     pts = np.stack((X.reshape(-1), Y.reshape(-1), Z.reshape(-1)), axis=1)
     vol = compute_vol(mins, maxs, grid_size, conf, **kw)
     return pts, vol.cpu().numpy()
+
+
+def create_mesh_from_volume(volume, level, mins, maxs, G, gradient_direction="ascent"):
+    """`create_mesh_from_volume` (extract_by_mc.py:36-43, its signature and default): marching cubes over `volume` (G, G, G),
+    a numpy array or a tensor, at `level`, the vertices scaled into the box `mins` ... `maxs` (:41).  Returns
+    (verts (V, 3) float32, faces (F, 3) int32) on the device -- no trimesh object, no normals (`save_attributed_mesh` takes
+    them from the net).  See `mc.marching_cubes` for the rule and what is UNPINNED."""
+    from . import mc
+    if tuple(volume.shape) != (int(G),) * 3:
+        raise ValueError(f"volume of shape {tuple(volume.shape)} is not the ({G}, {G}, {G}) lattice the scale is formed for")
+    return mc.marching_cubes(volume, level, gradient_direction, mins, maxs)
 
 
 def _place(v, dim):
@@ -260,3 +276,19 @@ def extract(dirname, fname, conf, verts, faces, train=False, source=None):
         for k in range(min(len(meshes), 5) - 1, -1, -1):
             fpath = save_attributed_mesh(dirname, fname, meshes[k][0], meshes[k][1], conf, train, "trimmed", k)
     return fpath
+
+
+def extract_scene(dirname, fname, conf, train=False, source=None):
+    """The reference's whole `extract` (extract_by_mc.py:263-288), from the loaded parameters to the files: the SDF volume
+    over [-r, r]^3, r = `renderer.bounding_sphere_radius`, at `extraction.rough_grid_size` (train) or `extraction.grid_size`
+    points per axis, marching cubes at `extraction.level` with `extraction.gradient_direction`, then `extract` with that
+    mesh.  ValueError when the level set does not cross the volume.  Returns the last mesh path."""
+    radius = float(conf.renderer.bounding_sphere_radius)
+    mins, maxs = np.asarray([-radius] * 3), np.asarray([+radius] * 3)
+    G = int(conf.extraction.rough_grid_size if train else conf.extraction.grid_size)
+    vol = compute_vol(mins, maxs, G, conf)
+    verts, faces = create_mesh_from_volume(vol, conf.extraction.level, mins, maxs, G, conf.extraction.gradient_direction)
+    if faces.shape[0] == 0:
+        lo, hi = (float(v) for v in torch.aminmax(vol))
+        raise ValueError(f"no surface at level {conf.extraction.level}: the volume's values span [{lo}, {hi}]")
+    return extract(dirname, fname, conf, verts, faces, train, source)

@@ -127,6 +127,10 @@ SIGS = {
     "trim_faces": "lqxlqqqq",
     # F faces N slots keys owner labels status
     "face_components": "lqllxqqq",
+    # Gx Gy Gz vol level table code(uint16) block_sums[2 nb] counts[4]
+    "mc_count": "iiipfxxqq",
+    # Gx Gy Gz vol level table code block_offsets scale[3] mins[3] ascent vertex_base verts V faces F
+    "mc_emit": "iiipfxxqFFiqplql",
     "solver_adam_begin": "xffqq",
     # n w g m v alpha_t beta1 beta2 eps decay zero_grad state
     "solver_adam": "lppppfffffix",
@@ -294,7 +298,8 @@ def symbols():
                                             "ndjir_mlp_chain_workspace", "ndjir_mlp_set_math", "ndjir_mlp_get_math",
                                             "ndjir_mlp_set_tile_rows", "ndjir_mlp_get_tile_rows", "ndjir_mlp_set_chain_pipeline", "ndjir_mlp_get_chain_pipeline", "ndjir_mlp_pack_entry_bytes",
                                             "ndjir_mlp_debug_timeline", "ndjir_mlp_chain_kernel", "ndjir_mlp_chain_bias_partials", "ndjir_loss_terms_workspace",
-                                            "ndjir_mlp_chain_group_begin", "ndjir_mlp_chain_group_end", "ndjir_sparse_rows_header"]
+                                            "ndjir_mlp_chain_group_begin", "ndjir_mlp_chain_group_end", "ndjir_sparse_rows_header",
+                                            "ndjir_mc_case_table"]
 
 
 def hash_num_params(G0, growth_factor, T0, L, D):
