@@ -319,7 +319,7 @@ class PixelCompose(Function):
         B, R, _ = pix.shape
         args = [_c(pix), _c(env), _c(spec)]
         color = torch.empty((B, R, 3), device=pix.device, dtype=torch.float32)
-        lib.call("render_pixel_compose", B * R, env.shape[-1], int(entangle), *args, _c(bg), color)
+        lib.call("render_pixel_compose", B * R, env.shape[-1], int(entangle), *args, None if bg is None else _c(bg), color)
         ctx.save_for_backward(*args)
         ctx.cfg = (B, R, env.shape[-1], int(entangle))
         return color
