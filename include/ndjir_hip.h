@@ -828,6 +828,74 @@ int ndjir_mc_emit(int Gx, int Gy, int Gz, const float* vol, float level, const u
                   const int* block_offsets, const float* scale, const float* mins, int ascent, int* vertex_base, float* verts,
                   long long V, int* faces, long long F, hipStream_t stream);
 
+/* ---- Chamfer evaluation (chamfer.hip; python/evaluate_chamfer_dtumvs.py:84-175: sample, thin, mask, nearest) -----------
+ * Every point array is (n, 3) fp64 on the device.  All coordinate arithmetic is fp64, one rounding per operation in the
+ * order of the reference's numpy expressions (no contraction).  Every count below is at most 2^31 - 1.
+ *
+ * A GRID is an origin (HOST, 3 doubles), a cell size h > 0 and dims (HOST, 3 long long, each in [1, 2^20]): the cell of p
+ * along axis a is floor((p[a] - origin[a]) / h) clamped to [0, dims[a]), its key (cx dims[1] + cy) dims[2] + cz.  The grid
+ * is sparse: the caller sorts the points by key (ndjir_chamfer_cell_keys, then any sort) and passes the sorted points and
+ * keys; a cell is found by a binary search, the cells (cx, cy, z0 .. z1) are one contiguous run.
+ *
+ * Exclusive prefix sums of n ints: offsets[i] = vals[0] + ... + vals[i - 1].  counts (2 ints on the device): [0] = the total
+ * capped at 2^31 - 1, [1] != 0 if it exceeds that (offsets are then meaningless).  workspace: ceil(n / 1024) ints.  Each
+ * value must be in [0, 2^15 + 1). */
+int ndjir_chamfer_scan(long long n, const int* vals, int* offsets, int* workspace, int* counts, hipStream_t stream);
+/* Sampling, pass 1 (:92-103): verts (N, 3) fp64, faces (F, 3) int32.  Per triangle v1 = p1 - p0, v2 = p2 - p0, l = |v| (the
+ * squares summed left to right), area2 = |v1 x v2|; a triangle with area2 > 0 false yields nothing; thr = thresh *
+ * sqrt(l1 * l2 / area2), n1 = floor(l1 / thr), n2 = floor(l2 / thr).  rows[t] = n1 + 1, the number of candidate rows i (0 if
+ * the triangle yields nothing, which includes n1 == 0 or n2 == 0: the reference then divides by 1e-7 and no candidate
+ * passes); n2[t] = n2.  CAP: n1, n2 <= 32767 per triangle, so a triangle has at most 2^30 candidates.  flags (2 ints on
+ * the device): [0] != 0 if a triangle exceeds the cap (or its n is not a number), [1] != 0 if a face names a vertex outside
+ * [0, N) (such a face yields nothing). */
+int ndjir_chamfer_tri_rows(long long N, const double* verts, long long F, const int* faces, double thresh, int* rows, int* n2,
+                           int* flags, hipStream_t stream);
+/* Pass 2, one lane per candidate row r of all R = sum(rows): tri_row_off = the prefix sums of rows; row_tri[r] = its triangle
+ * t, i = r - tri_row_off[t]; row_cnt[r] = the number of j in [0, n2] with (i + 0.5) / max(n1, 1e-7) + (j + 0.5) / max(n2, 1e-7)
+ * < 1 evaluated in fp64 as written (:34-39).  The kept j are a prefix (the rounded sum does not decrease with j), found by
+ * bisection: no lane loops over the candidates. */
+int ndjir_chamfer_row_counts(long long F, const int* rows, const int* n2, const int* tri_row_off, long long R, int* row_tri,
+                             int* row_cnt, hipStream_t stream);
+/* Pass 3: row_pt_off = the prefix sums of row_cnt, S their total; points (S, 3): point (v1 k0 + v2 k1) + p0 (:40) of row r,
+ * candidate j at row_pt_off[r] + j -- the order (triangle, i, j) of the reference, no atomics.  One lane per row writes its
+ * row_cnt[r] <= 32768 points; stores are guarded by S. */
+int ndjir_chamfer_emit_points(long long N, const double* verts, const int* faces, const int* rows, const int* n2,
+                              const int* tri_row_off, long long R, const int* row_tri, const int* row_cnt, const int* row_pt_off,
+                              long long S, double* points, hipStream_t stream);
+/* keys[i] = the grid key of points[i] (int64). */
+int ndjir_chamfer_cell_keys(long long N, const double* points, const double* origin, double h, const long long* dims,
+                            long long* keys, hipStream_t stream);
+/* One round of the greedy thinning (:124-133) as a parallel iteration.  points and keys sorted by key in the grid (origin,
+ * thresh, dims); rank[i] = the position of point i in the processing order (a permutation).  States, one byte per point:
+ * 0 undecided, 1 kept, 2 dropped; the first round starts from zeros.  From state_in only (state_out is a second buffer): an
+ * undecided point with a KEPT neighbour of smaller rank becomes dropped; one whose neighbours of smaller rank are all
+ * dropped becomes kept; else it stays.  Neighbour: dx dx + dy dy + dz dz <= thresh thresh in fp64, the point itself
+ * excluded; the 27 cells around the point are visited (one more layer where the point lies within 2^-20 of a cell wall,
+ * which covers the rounding of the cell coordinate).  undecided (1 int on the device) = the points still undecided in
+ * state_out.  The undecided point of smallest rank is always decided, so the caller repeats, swapping the buffers, until
+ * undecided == 0, and the kept points are the reference's for that order.  No block waits for another. */
+int ndjir_chamfer_thin_round(long long N, const double* points, const long long* keys, const int* rank, const double* origin,
+                             double thresh, const long long* dims, const unsigned char* state_in, unsigned char* state_out,
+                             int* undecided, hipStream_t stream);
+/* Observation-mask filter (:141-149).  lo, hi, bb0: HOST, 3 doubles each: lo = BB[0] - patch and hi = BB[1] + 2 patch as the
+ * reference rounds them (fp32), bb0 = BB[0]; mask (dims[0], dims[1], dims[2]) uint8, C order.  in_bb[i] = all(p >= lo) &
+ * all(p < hi); in_obs[i] = in_bb & every g = rint((p - bb0) / res) (half to even) in [0, dims) & mask[g] != 0. */
+int ndjir_chamfer_mask_points(long long N, const double* points, const double* lo, const double* hi, const double* bb0, double res,
+                              const int* dims, const unsigned char* mask, unsigned char* in_bb, unsigned char* in_obs,
+                              hipStream_t stream);
+/* Ground-plane filter (:166-170): above[i] = ((P0 x + P1 y) + P2 z) + P3 * 1 > 0; plane: HOST, 4 doubles. */
+int ndjir_chamfer_above_plane(long long N, const double* points, const double* plane, unsigned char* above, hipStream_t stream);
+/* Nearest target closer than max_dist, one query per lane.  targets (T >= 1) and keys sorted by key in the grid (origin, h,
+ * dims); max_dist <= 64 h.  dist[q] = sqrt of the smallest fp64 dx dx + dy dy + dz dz over the targets, idx[q] = that
+ * target's position in the SORTED array, if dist < max_dist; else dist = +inf, idx = -1 (also for a query that is not a
+ * number).  The minimum is exact: the cells are searched shell by shell (Chebyshev distance s from the query's cell) until
+ * the best distance is no greater than the shell's lower bound (s - 1) h, or that bound reaches max_dist; columns whose own
+ * lower bound rules them out are skipped.  A far query therefore costs at most (2 ceil(max_dist / h) + 3)^3 cell probes, a
+ * query next to the cloud about 27; a probe is one binary search over the keys. */
+int ndjir_chamfer_nearest(long long Q, const double* queries, long long T, const double* targets, const long long* keys,
+                          const double* origin, double h, const long long* dims, double max_dist, double* dist, int* idx,
+                          hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,11 +18,12 @@ _vp = ctypes.c_void_p
 _CT = {"i": ctypes.c_int, "f": ctypes.c_float, "p": _vp, "q": _vp, "F": ctypes.POINTER(ctypes.c_float),
        "I": ctypes.POINTER(ctypes.c_int), "l": ctypes.c_longlong, "P": ctypes.POINTER(_vp),
        "A": ctypes.POINTER(ctypes.c_int), "L": ctypes.POINTER(ctypes.c_longlong), "x": _vp,
-       "W": ctypes.POINTER(ctypes.c_float), "u": ctypes.c_uint, "s": ctypes.c_char_p}
+       "W": ctypes.POINTER(ctypes.c_float), "u": ctypes.c_uint, "s": ctypes.c_char_p, "d": ctypes.c_double,
+       "D": ctypes.POINTER(ctypes.c_double)}
 
 # signature strings (without the trailing stream): i=int f=float l=long long p=device pointer
 # F=float[3] host  I=int[3] host  q=int32 device pointer (nullable)  x=device pointer of any dtype
-# P=host array of device pointers  A=host int array  L=host long long array
+# P=host array of device pointers  A=host int array  L=host long long array  d=double  D=host double array
 _VOX_TAIL, _PLN_TAIL, _HSH_TAIL = "IiFFi", "iiFFi", "ifiiiFFi"
 
 
@@ -131,6 +132,24 @@ SIGS = {
     "mc_count": "iiipfxxqq",
     # Gx Gy Gz vol level table code block_offsets scale[3] mins[3] ascent vertex_base verts V faces F
     "mc_emit": "iiipfxxqFFiqplql",
+    # n vals offsets workspace counts[2]
+    "chamfer_scan": "lqqqq",
+    # N verts(fp64) F faces thresh rows n2 flags[2]
+    "chamfer_tri_rows": "lxlqdqqq",
+    # F rows n2 tri_row_off R row_tri row_cnt
+    "chamfer_row_counts": "lqqqlqq",
+    # N verts faces rows n2 tri_row_off R row_tri row_cnt row_pt_off S points(fp64)
+    "chamfer_emit_points": "lxqqqqlqqqlx",
+    # N points(fp64) origin[3] h dims[3] keys(int64)
+    "chamfer_cell_keys": "lxDdLx",
+    # N points keys rank origin[3] thresh dims[3] state_in state_out undecided[1]
+    "chamfer_thin_round": "lxxqDdLxxq",
+    # N points lo[3] hi[3] bb0[3] res dims[3] mask in_bb in_obs
+    "chamfer_mask_points": "lxDDDdAxxx",
+    # N points plane[4] above
+    "chamfer_above_plane": "lxDx",
+    # Q queries T targets keys origin[3] h dims[3] max_dist dist(fp64) idx
+    "chamfer_nearest": "lxlxxDdLdxq",
     "solver_adam_begin": "xffqq",
     # n w g m v alpha_t beta1 beta2 eps decay zero_grad state
     "solver_adam": "lppppfffffix",
@@ -262,13 +281,15 @@ def _marshal(name, sig, args):
             if not (v.is_cuda and v.is_contiguous()):
                 raise NdjirHipError(f"ndjir_{name}: expected a contiguous GPU tensor")
             cargs.append(v.data_ptr())
+        elif c == "D":     # host double array
+            cargs.append((ctypes.c_double * len(v))(*[float(x) for x in v]))
         elif c == "W":     # host float array
             cargs.append((ctypes.c_float * len(v))(*[float(x) for x in v]))
         elif c == "F":
             cargs.append(_f3(v))
         elif c == "I":
             cargs.append(_i3(v))
-        elif c == "f":
+        elif c in "fd":
             cargs.append(float(v))
         else:
             cargs.append(int(v))

@@ -1,4 +1,5 @@
-"""Writers of the mesh export: Wavefront OBJ with per-vertex colours, 8-bit PNG, the environment map's min/max note.
+"""Writers of the mesh export: Wavefront OBJ with per-vertex colours, 8-bit PNG, the environment map's min/max note; and the
+reader of a PLY point cloud's positions (`read_ply_points`, the scan of the Chamfer evaluation).
 
 Reference: `mesh.export(fpath, "obj")` through trimesh (python/extract_by_mc.py:217-219) and `cv.imwrite`
 (:257-258).  BOTH FORMATS ARE UNPINNED: neither trimesh nor cv2 is available here, so the bytes of the reference's files
@@ -67,6 +68,57 @@ def read_obj(path):
     return dict(verts=v[:, :3], colors=v[:, 3:6] if v.shape[1] >= 6 else None,
                 normals=np.asarray(vn, dtype=np.float32).reshape(-1, 3) if vn else None,
                 faces=np.asarray(f, dtype=np.int64).reshape(-1, 3))
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+
+
+def read_ply_points(path):
+    """The vertex positions of a PLY file, (N, 3) float64 (`o3d.io.read_point_cloud(...).points`,
+    python/evaluate_chamfer_dtumvs.py:153-154): `format ascii 1.0` or `binary_little_endian 1.0`, the `vertex` element
+    first, scalar properties only in it; `x`, `y`, `z` are read, every other property (DTU's `stl###_total.ply` carries
+    normals and colours) and every later element is skipped."""
+    with open(path, "rb") as fp:
+        if fp.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, n_vertex, props, element, elements = None, None, [], None, []
+        while True:
+            line = fp.readline()
+            if not line:
+                raise ValueError(f"{path}: the header does not end")
+            t = line.decode("ascii", errors="replace").split()
+            if not t or t[0] in ("comment", "obj_info"):
+                continue
+            if t[0] == "end_header":
+                break
+            if t[0] == "format":
+                fmt = t[1]
+            elif t[0] == "element":
+                element = t[1]
+                elements.append(element)
+                if element == "vertex":
+                    n_vertex = int(t[2])
+            elif t[0] == "property" and element == "vertex":
+                if t[1] == "list" or t[1] not in _PLY_TYPES:
+                    raise ValueError(f"{path}: vertex property {' '.join(t[1:])} is not a scalar")
+                props.append((t[2], _PLY_TYPES[t[1]]))
+        names = [n for n, _ in props]
+        if n_vertex is None or elements[0] != "vertex" or any(a not in names for a in "xyz"):
+            raise ValueError(f"{path}: the first element must be `vertex` with properties x, y, z")
+        if fmt == "ascii":
+            rows = np.loadtxt(fp, dtype=np.float64, max_rows=n_vertex, ndmin=2) if n_vertex else np.zeros((0, len(props)))
+            if rows.shape != (n_vertex, len(props)):
+                raise ValueError(f"{path}: expected {n_vertex} vertex rows of {len(props)} numbers")
+            return np.ascontiguousarray(rows[:, [names.index(a) for a in "xyz"]])
+        if fmt != "binary_little_endian":
+            raise ValueError(f"{path}: format {fmt} is not supported (ascii, binary_little_endian)")
+        dtype = np.dtype([(n, "<" + c) for n, c in props])
+        rows = np.frombuffer(fp.read(n_vertex * dtype.itemsize), dtype=dtype)
+        if rows.shape[0] != n_vertex:
+            raise ValueError(f"{path}: expected {n_vertex} vertices, found {rows.shape[0]}")
+        return np.stack([rows[a].astype(np.float64) for a in "xyz"], axis=1)
 
 
 def _chunk(tag, data):
